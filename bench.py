@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X-native DreamerV3 world-model training hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2] [--dump-outputs DIR] [--full]
 
 A "step" is ONE full training update of the reference's Dreamer._train (dreamer.py:192-200) on one
 synthetic replay minibatch already resident in HBM: world-model forward/backward (CNN encoder, RSSM
@@ -10,9 +10,15 @@ update on the updated world model (imagination over H, lambda-returns, actor and
 forward/backward, two clip+Adam steps) -- and, for N > 1, one gradient all-reduce (RCCL) per
 optimizer.  The metric is BASELINE.json's: imagination-steps/s = N_gpus * B*T*H / time per update.
 
-Prints ONE JSON line on rank 0 with the `roofline` (dominant MFMA kernel, measured live with HIP
-events on the launch stream) and `cpu_baseline` (the CPU oracle timed on this box's host cores)
-objects described in DESIGN.md.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps, writes the last
+step's outputs when --dump-outputs is given, and prints the headline.  --full adds the legs that
+take runs of their own: the `roofline` (dominant MFMA kernel, measured live with HIP events on the
+launch stream), the phase `timers`, the host-staged rate, the other BASELINE `configs` (--also) and
+`cpu_baseline` (the CPU oracle timed on this box's host cores), the objects described in DESIGN.md.
+
+--dump-outputs DIR: after the timed steps, what the last one handed its caller -- the metrics, the
+posterior and every updated parameter of the world model, actor and critics -- as DIR/<name>.npy
+(float32, metrics float64); tensors above DUMP_CAP elements as a fixed, seeded sample of DUMP_CAP.
 """
 from __future__ import annotations
 
@@ -48,6 +54,40 @@ def synthetic_batch(name, seed, device):
     from dv3hip import shapes
 
     return {k: torch.from_numpy(v).to(device) for k, v in shapes.synthetic_batch(name, seed).items()}
+
+
+DUMP_CAP = 1 << 16  # elements per dumped tensor, <= 256 KB each (cfg2: 115 arrays, 7.5 MB in all)
+
+
+def dump_outputs(out_dir, runner, wm, beh):
+    """The last timed step's outputs as out_dir/<name>.npy.  The sample of a larger tensor depends only on its name and
+    size, so two builds of the project write the same elements."""
+    import zlib
+
+    os.makedirs(out_dir, exist_ok=True)
+
+    def put(name, v):
+        fname = os.path.join(out_dir, name.replace("/", ".") + ".npy")
+        if not torch.is_tensor(v):
+            np.save(fname, np.asarray(v, dtype=np.float64))
+            return
+        flat = v.detach().reshape(-1)
+        if flat.numel() > DUMP_CAP:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            idx = np.sort(rng.choice(flat.numel(), DUMP_CAP, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(fname, flat.float().cpu().numpy())
+
+    torch.cuda.synchronize()
+    for k, v in sorted(runner.last_metrics.items()):
+        put("metrics." + k, v.detach().double().cpu().numpy() if torch.is_tensor(v) else v)
+    for k, v in sorted((runner.last_post or {}).items()):
+        put("post." + k, v)
+    for k, v in wm.state_dict().items():
+        put("wm." + k, v)
+    for k, v in beh.state_dict().items():
+        if not k.startswith("_world_model."):
+            put("beh." + k, v)
 
 
 def host_cores() -> int:
@@ -292,11 +332,17 @@ def main():
     ap.add_argument("--serial", action="store_true",
                     help="time whole updates one after the other (no two-update pipeline): r01-r03's timed region")
     ap.add_argument("--by-shape", action="store_true", help="roofline leg: key GEMM launches by (M,N,K) too")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, phase-timer, host-staging, other-config (--also) and cpu legs after the "
+                         "headline; without it a run is only the warm-up and the timed updates")
     ap.add_argument("--plain", action="store_true",
-                    help="only the warm-up and timed updates (no roofline / phase-timer / staging / cpu legs): the "
-                         "command tools/run_trace.sh puts under rocprofv3 so that every traced launch belongs to an update")
+                    help="only the warm-up and timed updates, even with --full: the command tools/run_trace.sh puts "
+                         "under rocprofv3 so that every traced launch belongs to an update")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--also", default="cfg1,cfg3,cfg4,cfg5",
-                    help="further BASELINE configs measured in the same run on one GPU, comma-separated ('none' = skip)")
+                    help="with --full: further BASELINE configs measured in the same run on one GPU, comma-separated "
+                         "('none' = skip)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -369,17 +415,35 @@ def main():
     launch = launch_name(runner, mode)
     if not np.isfinite(loss):
         raise SystemExit("non-finite loss in the timed region")
+    if args.dump_outputs and rank == 0:  # (before any --full leg trains further)
+        dump_outputs(args.dump_outputs, runner, wm, beh)
 
-    # ---- roofline leg: per-launch HIP-event timing of one more (eager) update on the launch stream
-    roofline = None
-    if args.plain:
+    units = world * B * T * H
+    head = {
+        "metric": METRIC, "value": units * args.steps / elapsed, "unit": "imagination-steps/s",
+        "n_gpus": world, "ranks": dist.get_world_size() if world > 1 else 1,
+        "backend": (dist.get_backend() if world > 1 else None), "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"{name}: {WORKLOADS.get(name, name)}, RSSM deter={shape['deter']} hidden="
+                               f"{shape['hidden']} stoch={shape['stoch']}x{shape['discrete']}, "
+                               f"{'one-hot' if shape['actor_dist'] == 'onehot' else 'continuous'} actor ({shape['A']}), "
+                               f"imag_gradient {shape['imag_gradient']}, batch {B} x seq {T} per GPU, horizon {H}; "
+                               "one step = full Dreamer._train update (world model + actor + critic fwd/bwd, "
+                               "gradient all-reduce, 3x clip+Adam)",
+                   "global_batch": B * world, "seq_len": T, "horizon": H, "parallelism": f"dp{world}",
+                   "launch": launch},
+        "warmup_extra_for_capture": extra_warm, "model_loss": loss,
+    }
+    if args.plain or not args.full:
         if rank == 0:
-            print(json.dumps({"metric": METRIC, "value": world * B * T * H * args.steps / elapsed, "n_gpus": world,
-                              "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-                              "config": {"workload": name, "launch": launch}, "plain": True}))
+            print(json.dumps(head))
         if world > 1:
             dist.destroy_process_group()
         return
+
+    # ---- roofline leg: per-launch HIP-event timing of one more (eager) update on the launch stream
+    roofline = None
     if rank != 0:
         runner.step(data, eager=True)  # every rank takes part in the profiled update's all-reduces
         torch.cuda.synchronize()
@@ -557,25 +621,7 @@ def main():
         cpu = cpu_baseline(name)
 
     if rank == 0:
-        units = world * B * T * H
-        out = {
-            "metric": METRIC, "value": units * args.steps / elapsed, "unit": "imagination-steps/s",
-            "n_gpus": world, "ranks": dist.get_world_size() if world > 1 else 1,
-            "backend": (dist.get_backend() if world > 1 else None), "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"{name}: {WORKLOADS.get(name, name)}, RSSM deter={shape['deter']} hidden="
-                                   f"{shape['hidden']} stoch={shape['stoch']}x{shape['discrete']}, "
-                                   f"{'one-hot' if shape['actor_dist'] == 'onehot' else 'continuous'} actor ({shape['A']}), "
-                                   f"imag_gradient {shape['imag_gradient']}, batch {B} x seq {T} per GPU, horizon {H}; "
-                                   "one step = full Dreamer._train update (world model + actor + critic fwd/bwd, "
-                                   "gradient all-reduce, 3x clip+Adam)",
-                       "global_batch": B * world, "seq_len": T, "horizon": H, "parallelism": f"dp{world}",
-                       "launch": launch},
-            "warmup_extra_for_capture": extra_warm, "model_loss": loss, "timers": timers,
-            "roofline": roofline, "cpu_baseline": cpu, "configs": others,
-        }
-        print(json.dumps(out))
+        print(json.dumps(dict(head, timers=timers, roofline=roofline, cpu_baseline=cpu, configs=others)))
     if world > 1:
         dist.destroy_process_group()
 

@@ -18,6 +18,22 @@ WM_PREFIXES = ("encoder", "dynamics", "heads")
 from dv3hip.shapes import make_config, obs_space  # noqa: E402,F401  (moved into the package: bench.py needs no tests/)
 
 
+def host_threads() -> int:
+    """Threads for the CPU oracle: this process's CPU share (affinity, cgroup quota, OMP_NUM_THREADS).  os.cpu_count()
+    counts the whole machine; a torch thread pool larger than the share the process may use stalls in its barriers."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()
+        if quota != "max":
+            n = min(n, int(quota) // int(period))
+    except (OSError, ValueError):
+        pass
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and int(omp) > 0:
+        n = min(n, int(omp))
+    return max(1, n)
+
+
 def build_models(name, device="cuda:0", weights=None):
     """-> (config, WorldModel, ImagBehavior) on the GPU with common.make_weights(name) loaded."""
     import models

@@ -134,7 +134,7 @@ def test_bench_launches_its_own_ranks():
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "3",
-                        "--config", "tiny", "--no-cpu-baseline"], env=dict(env, DV3_DIST_BACKEND="gloo"),
+                        "--config", "tiny", "--no-cpu-baseline", "--full"], env=dict(env, DV3_DIST_BACKEND="gloo"),
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -31,7 +31,12 @@ def test_constructors_reproduce_the_reference_initialisation(name):
         a = v.detach().numpy().astype(np.float64).reshape(-1)
         cs, ref = common.checksum(a), G[f"{name}/sum/{k}"]
         assert np.allclose(cs, ref, rtol=1e-6, atol=1e-9), f"{name} {k}: {cs} vs {ref}"
-        assert np.array_equal(a[:4].astype(np.float32), G[f"{name}/head/{k}"]), f"{name} {k}: first values differ"
+        # (within 4 float32 ulps: torch's vectorised erfinv behind trunc_normal_ differs in the last bit between host
+        # CPUs; another draw or another order would differ by far more)
+        head, ref_head = a[:4].astype(np.float32), G[f"{name}/head/{k}"]
+        assert ref_head.dtype == np.float32 and head.shape == ref_head.shape, f"{name} {k}: first values differ"
+        ulps = np.abs(head.view(np.int32).astype(np.int64) - ref_head.view(np.int32).astype(np.int64))
+        assert np.all(np.sign(head) == np.sign(ref_head)) and ulps.max() <= 4, f"{name} {k}: first values differ"
 
 
 def test_weight_init_statistics():

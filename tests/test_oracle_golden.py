@@ -208,8 +208,10 @@ def test_full_size_slices_and_checksums(name):
     """Full-size configs: stored row slices + whole-tensor checksums of the reference's outputs, world model and
     behaviour (imagination rows, lambda-returns, losses) -- this is what pins the oracle the GPU tests use at
     BASELINE sizes (cfg 3: deter 1024, 18-way one-hot actor, reinforce, batch 32)."""
+    from tests import helpers as Hh
+
     g = load(name)
-    torch.set_num_threads(max(1, os.cpu_count() or 1))
+    torch.set_num_threads(Hh.host_threads())
     with torch.no_grad():
         cfg, p, n, data, out = wm_out(name)
     sel = slice(0, 2)
@@ -257,7 +259,7 @@ def test_crafter_width_gradients_and_update(name):
     from tests import helpers as Hh
 
     g = load(name)
-    torch.set_num_threads(max(1, os.cpu_count() or 1))
+    torch.set_num_threads(Hh.host_threads())
     r = Hh.oracle_update(name, piecewise=True)
     for k, v in r["wm_grads"].items():
         check_sum(g, "grad/" + k, v.numpy(), tol=2e-4)

@@ -1,42 +1,69 @@
-"""Build-container check (skipped where /root/reference is absent, e.g. on the GPU box): the reference's own causal
-world models -- scm_world_model.WorldModelWithSCM (scm_world_model.py:407) and causal_VAE.CausalVAE_WorldModel
-(causal_VAE.py:858) -- import and CONSTRUCT against this repo's `networks` / `tools`.  They stay
-the integrator's files; what is pinned here is that the class surface they build on (RSSM / MultiEncoder /
-MultiDecoder / MLP constructors and private members, tools.Optimizer) is the reference's.  The reference files are
-imported from where they lie, in a child process (its sys.path / sys.modules stay its own); nothing is copied."""
+"""The reference's own causal world models -- scm_world_model.WorldModelWithSCM (scm_world_model.py:407) and
+causal_VAE.CausalVAE_WorldModel (causal_VAE.py:858) -- build on this repo's `networks` / `tools`.
+They stay the integrator's files; what is pinned here is that the class surface they build on (RSSM / MultiEncoder /
+MultiDecoder / MLP constructors and private members, tools.Optimizer) is the reference's.  Every constructor call
+they make at the tiny config was recorded from the reference itself (tests/golden/causal_construct.json, written by
+tests/golden/make_causal_golden.py from a reference checkout) and is replayed here on these modules."""
+import json
 import os
-import subprocess
-import sys
-import textwrap
 
-import pytest
+HERE = os.path.dirname(os.path.abspath(__file__))
+FIXTURE = json.load(open(os.path.join(HERE, "golden", "causal_construct.json")))
+SURFACE = json.load(open(os.path.join(HERE, "golden", "surface.json")))
+CAUSAL_FILES = ("scm_world_model.py", "causal_VAE.py")
+# SCMRSSM's own methods (tests/test_surface_cpu.py OUTSIDE): not members of networks.RSSM
+SCM_ONLY = {"intervene", "remove_intervention"}
 
-REFERENCE = "/root/reference"
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+def decode(v, params):
+    if isinstance(v, dict):
+        if set(v) == {"tuple"}:
+            return tuple(decode(x, params) for x in v["tuple"])
+        if set(v) == {"params"}:
+            return params()
+        if set(v) == {"device"}:
+            import torch
+
+            return torch.device(v["device"])
+        return {k: decode(x, params) for k, x in v.items()}
+    if isinstance(v, list):
+        return [decode(x, params) for x in v]
+    return v
 
 
-@pytest.mark.skipif(not os.path.isfile(os.path.join(REFERENCE, "scm_world_model.py")),
-                    reason="the reference checkout is only present in the build container")
 def test_reference_causal_world_models_construct_on_these_modules():
-    code = textwrap.dedent(f"""
-        import sys
-        sys.path.insert(0, {os.path.join(REPO, "dreamerv3-torch_amd")!r}); sys.path.insert(0, {REPO!r})
-        sys.path.append({REFERENCE!r})  # behind the package: networks / tools / models resolve to the MI355X modules
-        import torch
-        import networks, tools
-        from dv3hip import shapes
-        assert networks.__file__.startswith({REPO!r}) and tools.__file__.startswith({REPO!r})
-        import scm_world_model, causal_VAE
-        assert scm_world_model.__file__.startswith({REFERENCE!r}) and causal_VAE.__file__.startswith({REFERENCE!r})
-        cfg, obs = shapes.make_config("tiny", "cpu"), shapes.obs_space("tiny")
-        a = scm_world_model.WorldModelWithSCM(obs, None, 0, cfg)
-        b = causal_VAE.CausalVAE_WorldModel(obs, None, 0, cfg)
-        assert isinstance(b.dynamics, networks.RSSM) and isinstance(a.encoder, networks.MultiEncoder)
-        assert isinstance(a.dynamics._rssm, networks.RSSM) and isinstance(a.dynamics._rssm._cell, networks.GRUCell)
-        for m in (a, b):
-            assert isinstance(m._model_opt, tools.Optimizer) and sum(p.numel() for p in m.parameters()) > 0
-        print("constructed", type(a).__name__, type(b).__name__)
-    """)
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "constructed WorldModelWithSCM CausalVAE_WorldModel" in r.stdout
+    import torch
+
+    import networks
+    import tools
+
+    mods = {"networks": networks, "tools": tools}
+    rssm_used = {a for a, sites in SURFACE["RSSM"].items() if any(s.startswith(CAUSAL_FILES) for s in sites)}
+    assert set(FIXTURE) == {"WorldModelWithSCM", "CausalVAE_WorldModel"}
+    for model, rec in FIXTURE.items():
+        calls = rec["calls"]
+        assert {c["cls"] for c in calls} == {"networks.RSSM", "networks.MultiEncoder", "networks.MultiDecoder",
+                                             "networks.MLP", "tools.Optimizer"}, model
+        built = []
+
+        def params():
+            return (p for m in built for p in m.parameters())
+
+        for c in calls:
+            where = f"{model}.{c['path']}"
+            mname, cname = c["cls"].split(".")
+            cls = getattr(mods[mname], cname)
+            obj = cls(*decode(c["args"], params), **decode(c["kwargs"], params))
+            assert isinstance(obj, cls), where
+            if isinstance(obj, torch.nn.Module):
+                assert sum(p.numel() for p in obj.parameters()) == c["numel"], f"{where}: parameter count"
+                for sub, tname in c["children"].items():
+                    got = obj.get_submodule(sub)
+                    assert isinstance(got, getattr(networks, tname.split(".")[1])), f"{where}.{sub} is {type(got)}"
+                built.append(obj)
+            if isinstance(obj, networks.RSSM):
+                assert isinstance(obj._cell, networks.GRUCell), where
+                for a in sorted(rssm_used - SCM_ONLY):
+                    assert hasattr(obj, a), f"{where}: RSSM.{a} (used by the causal models) is missing"
+        assert isinstance(obj, tools.Optimizer) and calls[-1]["path"] == "_model_opt", model
+        assert sum(p.numel() for m in built for p in m.parameters()) > 0, model
