@@ -121,14 +121,17 @@ class Dreamer(nn.Module):
         """dreamer.py:116-188: eval -> mode of the task actor; training -> a sample of the exploration actor while
         `_should_expl` holds (for 'greedy' that IS the task actor), else of the task actor (the counterfactual branch
         behind `_best_candidate` is unreachable, SURVEY.md section 0 gotcha 2).  noise (tests): dict(prior, post [n_envs,S,D] ~ Exp(1); act [n_envs,A], N(0,1) or
-        Exp(1) for the one-hot actor) injected instead of the Philox stream."""
+        Exp(1) for the one-hot actor) injected instead of the Philox stream (continuous latents: prior, post [n_envs,S]
+        ~ N(0,1))."""
         latent, action = (None, None) if state is None else state
         nz = noise or {}
         obs = self._wm.preprocess(obs)
         embed = self._wm.encoder(obs)
         latent, _ = self._wm.dynamics.obs_step(latent, action, embed, obs["is_first"], noise=nz or None, prior=False)
-        if getattr(self._config, "eval_state_mean", False):
-            raise NotImplementedError("eval_state_mean needs continuous latents (dyn_discrete: 0)")
+        if getattr(self._config, "eval_state_mean", False):  # dreamer.py:129-131: act on the mean of the latent
+            if "mean" not in latent:
+                raise NotImplementedError("eval_state_mean needs continuous latents (dyn_discrete: 0)")
+            latent["stoch"] = latent["mean"]
         feat = self._wm.dynamics.get_feat(latent)
         if training and self._exploring():
             actor = self._expl_behavior.actor(feat)

@@ -255,6 +255,88 @@ class KLLossFn(Function):
 
 
 # ---------------------------------------------------------------------------------------------
+# continuous Gaussian latents (dyn_discrete: 0)
+# ---------------------------------------------------------------------------------------------
+class GaussHeadFn(Function):
+    """RSSM._suff_stats_layer's activations (networks.py:258-270) and the rsample / mode of get_dist(...)
+    (networks.py:167-171, 228-231) on the stat layer's raw output [..., 2S] -> (mean, std, stoch)."""
+
+    @staticmethod
+    def forward(ctx, raw, eps, rng, mean_act, std_act, min_std, mode):
+        r = raw.detach().to(F32).contiguous()
+        S = r.shape[-1] // 2
+        mk = lambda: torch.empty(r.shape[:-1] + (S,), device=r.device, dtype=F32)
+        mean, std, stoch = mk(), mk(), mk()
+        eps_used = None if mode else mk()
+        ops.gauss_head_fwd(r, stoch, mean, std, eps=None if eps is None else eps.detach().to(F32).contiguous(), rng=rng,
+                           eps_out=eps_used, mean_act=mean_act, std_act=std_act, min_std=min_std, mode=mode)
+        ctx.save_for_backward(r, eps_used if eps_used is not None else r)
+        ctx.cfg = (mean_act, std_act, bool(mode))
+        ctx.set_materialize_grads(False)
+        return mean, std, stoch
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dmean, dstd, dstoch):
+        r, eps = ctx.saved_tensors
+        mean_act, std_act, mode = ctx.cfg
+        S = r.shape[-1] // 2
+        shp = r.shape[:-1] + (S,)
+        draw = torch.empty_like(r)
+        if dmean is None and dstd is None and dstoch is None:
+            return draw.zero_(), None, None, None, None, None, None
+        cc = lambda t: None if t is None else _c(t.reshape(shp))
+        ops.gauss_head_bwd(r, draw, dstoch=cc(dstoch), dmean=cc(dmean), dstd=cc(dstd), eps=None if mode else eps,
+                           mean_act=mean_act, std_act=std_act, mode=mode)
+        return draw, None, None, None, None, None, None
+
+
+class GaussEntropyFn(Function):
+    """Entropy of Normal(mean, std) summed over the last dim (tools.NormalLatent.entropy): sum (1/2 + 1/2 ln 2 pi +
+    ln std) from dv3_gauss_kl_fwd; d / d std = 1 / std, nothing reaches the mean."""
+
+    @staticmethod
+    def forward(ctx, mean, std):
+        m, s = mean.detach().to(F32).contiguous(), std.detach().to(F32).contiguous()
+        kl, ent = torch.empty(m.shape[:-1], device=m.device, dtype=F32), torch.empty(m.shape[:-1], device=m.device, dtype=F32)
+        ops.gauss_kl_fwd(m, s, m, s, kl, ent)  # (post = prior: the entropy is the kernel's second output)
+        ctx.save_for_backward(s)
+        return ent
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dent):
+        (s,) = ctx.saved_tensors
+        return None, dent.to(F32).unsqueeze(-1) / s
+
+
+class GaussKLFn(Function):
+    """networks.RSSM.kl_loss for continuous latents (networks.py:272-290 over Normal(mean, std)): gradient through
+    `loss` only, as KLLossFn."""
+
+    @staticmethod
+    def forward(ctx, post_mean, post_std, prior_mean, prior_std, free, dyn_scale, rep_scale):
+        t = [x.detach().to(F32).contiguous() for x in (post_mean, post_std, prior_mean, prior_std)]
+        kl = torch.empty(t[0].shape[:-1], device=t[0].device, dtype=F32)
+        ops.gauss_kl_fwd(*t, kl)
+        ctx.save_for_backward(*t, kl)
+        ctx.cfg = (float(free), float(dyn_scale), float(rep_scale))
+        clipped = torch.clip(kl, min=free)
+        return (dyn_scale + rep_scale) * clipped, kl.clone(), clipped, clipped.clone()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dloss, dvalue, ddyn, drep):
+        pm, ps, qm, qs, kl = ctx.saved_tensors
+        free, dyn_scale, rep_scale = ctx.cfg
+        outs = [torch.empty_like(pm) for _ in range(4)]
+        ops.gauss_kl_bwd(pm, ps, qm, qs, kl, dpost_mean=outs[0], dpost_std=outs[1], dprior_mean=outs[2],
+                         dprior_std=outs[3], free=free, dyn_scale=dyn_scale, rep_scale=rep_scale, upstream=1.0)
+        up = dloss.to(F32).reshape(kl.shape + (1,))
+        return tuple(o * up for o in outs) + (None, None, None)
+
+
+# ---------------------------------------------------------------------------------------------
 # RSSM.observe: the whole scan as one node (engine.RSSMEngine.observe_fwd / observe_bwd)
 # ---------------------------------------------------------------------------------------------
 def rssm_param_list(P: E.PRSSM) -> List[torch.Tensor]:
@@ -299,6 +381,39 @@ class ObserveFn(Function):
         gd = _c(d_dt, shape=(T, B, De), like=out["deter"])
         dembed = torch.empty(T, B, eng.E, device=dev, dtype=F32)
         side = eng.observe_bwd(dpl, dql, gs, gd, dembed)
+        side.join()
+        grads = [p.grad if ctx.needs_input_grad[7 + i] else None for i, p in enumerate(rssm_param_list(P))]
+        ctx.eng = ctx.out = None
+        return (dembed if ctx.needs_input_grad[0] else None, None, None, None, None, None, None) + tuple(grads)
+
+
+class ObserveGaussFn(Function):
+    """ObserveFn for continuous latents.  Outputs (post_stoch, post_mean, post_std, deter, prior_stoch, prior_mean,
+    prior_std), each [T,B,...]; eps_prior / eps_post [T,B,S] ~ N(0,1) or the rng stream."""
+
+    @staticmethod
+    def forward(ctx, embed_tm, action_tm, first_tm, eps_prior, eps_post, rng, dims, *params):
+        P = _rssm_shadow(params)
+        eng = E.RSSMEngine(P, E.Workspace(embed_tm.device), **dims)
+        emb = embed_tm.detach().to(F32).contiguous()
+        out = eng.observe_fwd(emb, action_tm.detach().to(F32).contiguous(), first_tm.detach().to(F32).contiguous(),
+                              q_prior=eps_prior, q_post=eps_post, rng=rng)
+        ctx.eng, ctx.P, ctx.out = eng, P, out
+        ctx.set_materialize_grads(False)
+        return tuple(out[k].clone() for k in ("post_stoch", "post_mean", "post_std", "deter", "prior_stoch",
+                                              "prior_mean", "prior_std"))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_ps, d_pm, d_psd, d_dt, d_qs, d_qm, d_qsd):
+        eng, P, out = ctx.eng, ctx.P, ctx.out
+        T, B, S, De = eng.T, eng.B, eng.S, eng.De
+        like = out["deter"]
+        cc = lambda t: None if t is None else _c(t.reshape(T, B, S))
+        gs = _c(d_ps, shape=(T, B, S), like=like)
+        gd = _c(d_dt, shape=(T, B, De), like=like)
+        dembed = torch.empty(T, B, eng.E, device=like.device, dtype=F32)
+        side = eng.observe_bwd((cc(d_pm), cc(d_psd)), (cc(d_qm), cc(d_qsd), cc(d_qs)), gs, gd, dembed)
         side.join()
         grads = [p.grad if ctx.needs_input_grad[7 + i] else None for i, p in enumerate(rssm_param_list(P))]
         ctx.eng = ctx.out = None

@@ -632,11 +632,21 @@ class MLPEngine:
 # ---------------------------------------------------------------------------------------------
 class RSSMEngine:
     def __init__(self, P: PRSSM, ws: Workspace, *, stoch: int, discrete: int, deter: int, hidden: int,
-                 num_actions: int, embed: int, unimix: float):
+                 num_actions: int, embed: int, unimix: float, mean_act: str = "none", std_act: str = "softplus",
+                 min_std: float = 0.1):
+        """discrete == 0: continuous Gaussian latents (networks.py:251-270).  The stochastic state is then S wide and
+        the stat layers 2S (mean_raw | std_raw); the scans below run their dense branches with ops.gauss_head_* in
+        place of the one-hot sampler and its straight-through backward, and none of the one-hot gathers / fusions."""
         self.P, self.ws = P, ws
         self.S, self.D, self.De, self.Hd, self.A, self.E = stoch, discrete, deter, hidden, num_actions, embed
-        self.SD = stoch * discrete
+        self.gauss = not discrete
+        self.SD = stoch if self.gauss else stoch * discrete  # width of the flattened stochastic state
+        self.SW = 2 * stoch if self.gauss else self.SD  # width of the stat layers' output
         self.unimix = unimix
+        self.head = dict(mean_act=mean_act, std_act=std_act, min_std=float(min_std))
+
+    def _head_bwd_kw(self):
+        return dict(mean_act=self.head["mean_act"], std_act=self.head["std_act"])
 
     # -- initial state (networks.py:99-123, 235-239): deter0 = tanh(W), stoch0 = mode(prior head) -----
     def init_state_fwd(self):
@@ -647,9 +657,12 @@ class RSSMEngine:
         x0 = ws.get("init.x0", (1, self.Hd))
         m0, r0 = ws.get("init.m", (1,)), ws.get("init.r", (1,))
         dense_ln_fwd(P.img_out, d0, None, x0pre, m0, r0, x0)
-        l0 = ws.get("init.logit", (1, self.SD))
+        l0 = ws.get("init.logit", (1, self.SW))
         ops.gemm(x0, P.ims.W, l0, bias=P.ims.b)
         s0 = ws.get("init.stoch", (1, self.SD))
+        if self.gauss:  # the initial stoch is the MEAN of the prior head (get_stoch -> dist.mode(), networks.py:235-239)
+            ops.gauss_head_fwd(l0, s0, mode=True, **self.head)
+            return s0, d0
         ops.onehot_sample(l0.view(self.S, self.D), s0.view(self.S, self.D), unimix=self.unimix, mode=True,
                           idx=ws.get("init.idx", (self.S,), torch.int32))
         return s0, d0
@@ -657,12 +670,15 @@ class RSSMEngine:
     def init_state_bwd(self, dstoch0, ddeter0):
         """dstoch0 [SD], ddeter0 [De] (accumulated by the scan) -> grads of W0 and the prior head."""
         P, ws = self.P, self.ws
-        l0, x0, x0pre, d0 = ws.get("init.logit", (1, self.SD)), ws.get("init.x0", (1, self.Hd)), \
+        l0, x0, x0pre, d0 = ws.get("init.logit", (1, self.SW)), ws.get("init.x0", (1, self.Hd)), \
             ws.get("init.x0pre", (1, self.Hd)), ws.get("init.deter", (1, self.De))
         m0, r0 = ws.get("init.m", (1,)), ws.get("init.r", (1,))
-        dl0 = ws.get("init.dlogit", (1, self.SD))
-        ops.onehot_st_bwd(l0.view(self.S, self.D), dstoch0.view(self.S, self.D), dl0.view(self.S, self.D),
-                          unimix=self.unimix, mode=True)
+        dl0 = ws.get("init.dlogit", (1, self.SW))
+        if self.gauss:
+            ops.gauss_head_bwd(l0, dl0, dstoch=dstoch0.view(1, self.S), mode=True, **self._head_bwd_kw())
+        else:
+            ops.onehot_st_bwd(l0.view(self.S, self.D), dstoch0.view(self.S, self.D), dl0.view(self.S, self.D),
+                              unimix=self.unimix, mode=True)
         dx0 = ws.get("init.dx0", (1, self.Hd))
         ops.gemm(dl0, P.ims.W, dx0, transB=False)
         lin_wgrad(P.ims.W, dl0, x0)
@@ -688,6 +704,11 @@ class RSSMEngine:
         S, D, SD, De, Hd, A, E = self.S, self.D, self.SD, self.De, self.Hd, self.A, self.E
         self.T, self.B = T, B
         TB = T * B
+        if self.gauss:
+            if force:
+                raise ValueError("teacher forcing is for the categorical draws: a Gaussian draw is injected as noise")
+            return self._observe_fwd_gauss(embed_tm, action_tm, first_tm, eps_prior=q_prior, eps_post=q_post, rng=rng,
+                                           state0=state0)
         force = force or {}
         f_post, f_prior, flips = force.get("post"), force.get("prior"), force.get("flips")
         s0, d0 = self.init_state_fwd()
@@ -778,6 +799,76 @@ class RSSMEngine:
         return dict(post_stoch=post_stoch, post_logit=post_logit, deter=deter, prior_stoch=prior_stoch,
                     prior_logit=prior_logit, action=ain, post_idx=post_idx)
 
+    def _observe_fwd_gauss(self, embed_tm, action_tm, first_tm, *, eps_prior, eps_post, rng, state0):
+        """observe_fwd for continuous latents: the dense (no gather) branches of the scan above, step by step
+            [blend (t = 0 or wide cells)] -> img_in GEMM -> LN/SiLU -> GRU GEMM -> gates (+ next deter blend)
+            -> obs_out GEMM (deter half) -> LN/SiLU + stat GEMM (one launch where ops.scan_ln_gemm_ok(Hd, 2S))
+            -> gauss_head_fwd (+ next stoch blend)
+        eps_prior / eps_post [T,B,S] ~ N(0,1) or the rng stream.  The prior's sample is drawn although nothing
+        consumes it, as the reference does (networks.py:195, 228-229)."""
+        P, ws = self.P, self.ws
+        T, B = embed_tm.shape[0], embed_tm.shape[1]
+        S, De, Hd, A, E = self.S, self.De, self.Hd, self.A, self.E
+        self.T, self.B = T, B
+        TB = T * B
+        s0, d0 = self.init_state_fwd()
+        first = ws.get("obs.first", (T, B))
+        first.copy_(first_tm)
+        if state0 is None:
+            first[0].fill_(1.0)
+        g = ws.get
+        sin, din, ain = g("obs.sin", (T, B, S)), g("obs.din", (T, B, De)), g("obs.ain", (T, B, A))
+        x1pre, x1 = g("obs.x1pre", (T, B, Hd)), g("obs.x1", (T, B, Hd))
+        m1, r1 = g("obs.m1", (T, B)), g("obs.r1", (T, B))
+        gpre, mg, rg = g("obs.gpre", (T, B, 3 * De)), g("obs.mg", (T, B)), g("obs.rg", (T, B))
+        deter = g("obs.deter", (T, B, De))
+        x3pre, x3 = g("obs.x3pre", (T, B, Hd)), g("obs.x3", (T, B, Hd))
+        m3, r3 = g("obs.m3", (T, B)), g("obs.r3", (T, B))
+        post_raw, post_eps = g("obs.post_raw", (T, B, 2 * S)), g("obs.post_eps", (T, B, S))
+        post_mean, post_std, post_stoch = g("obs.post_mean", (T, B, S)), g("obs.post_std", (T, B, S)), \
+            g("obs.post_stoch", (T, B, S))
+        ops.gemm(v2(embed_tm, E), P.obs_out.W[:, De:], v2(x3pre, Hd))
+        ops.reset_blend(v2(action_tm, A), None, first.view(TB), v2(ain, A))
+        fuse = ((De % 256 == 0 and De <= 1024) or (De % 1024 == 0 and De <= 4096)) and _FUSE_BLEND
+        fuse_row = _FUSE_SCAN_ROW and _FUSE_SCAN_LN and B <= 64 and ops.scan_ln_gemm_ok(Hd, 2 * S)
+        Cuts.mark("wm.fscan")
+        for t in range(T):
+            if T >= 16 and t == (3 * T) // 4:
+                Cuts.mark("wm.fscan2")
+            if t == 0 or not fuse:
+                prev_s = post_stoch[t - 1] if t > 0 else (None if state0 is None else state0[0])
+                prev_d = deter[t - 1] if t > 0 else (None if state0 is None else state0[1])
+                ops.obs_blend(prev_s, s0.view(S), prev_d, d0.view(De), action_tm[t], first[t], sin[t], din[t], ain[t])
+            nxt = fuse and t + 1 < T
+            dense_ln_fwd(P.img_in, sin[t], ain[t], x1pre[t], m1[t], r1[t], x1[t])
+            ops.gemm(x1[t], P.gru.W, gpre[t], A2=din[t])
+            ops.gru_fwd(gpre[t], P.gru.g, P.gru.b, din[t], deter[t], mg[t], rg[t],
+                        next_blend=(first[t + 1], d0.view(De), din[t + 1]) if nxt else None)
+            ops.gemm(deter[t], P.obs_out.W[:, :De], x3pre[t], accumulate=True)
+            if fuse_row:
+                ops.scan_ln_gemm(x3pre[t], P.obs_out.g, P.obs_out.b, x3[t], m3[t], r3[t], P.obs.W, post_raw[t],
+                                 bias=P.obs.b)
+            else:
+                ops.ln_act_fwd(x3pre[t], P.obs_out.g, P.obs_out.b, x3[t], m3[t], r3[t], act=True)
+                ops.gemm(x3[t], P.obs.W, post_raw[t], bias=P.obs.b)
+            ops.gauss_head_fwd(post_raw[t], post_stoch[t], post_mean[t], post_std[t],
+                               eps=None if eps_post is None else eps_post[t], rng=rng, eps_out=post_eps[t],
+                               next_blend=(first[t + 1], s0.view(S), sin[t + 1]) if nxt else None, **self.head)
+        Cuts.mark("wm.mid")
+        # prior head for all steps at once
+        x2pre, x2 = g("obs.x2pre", (T, B, Hd)), g("obs.x2", (T, B, Hd))
+        m2, r2 = g("obs.m2", (T, B)), g("obs.r2", (T, B))
+        prior_raw, prior_eps = g("obs.prior_raw", (T, B, 2 * S)), g("obs.prior_eps", (T, B, S))
+        prior_mean, prior_std, prior_stoch = g("obs.prior_mean", (T, B, S)), g("obs.prior_std", (T, B, S)), \
+            g("obs.prior_stoch", (T, B, S))
+        dense_ln_fwd(P.img_out, v2(deter, De), None, v2(x2pre, Hd), m2.view(TB), r2.view(TB), v2(x2, Hd))
+        ops.gemm(v2(x2, Hd), P.ims.W, v2(prior_raw, 2 * S), bias=P.ims.b)
+        ops.gauss_head_fwd(prior_raw, prior_stoch, prior_mean, prior_std, eps=eps_prior, rng=rng, eps_out=prior_eps,
+                           **self.head)
+        self._embed = embed_tm
+        return dict(post_stoch=post_stoch, post_mean=post_mean, post_std=post_std, post_raw=post_raw, deter=deter,
+                    prior_stoch=prior_stoch, prior_mean=prior_mean, prior_std=prior_std, prior_raw=prior_raw, action=ain)
+
     def lanes_pay(self, heavy_side: bool) -> bool:
         """Whether the reverse scan should run beside the deferred weight gradients on the two CU-masked lanes.
         Measured on MI355X (ms per update, lanes / in line): cfg 2 16.22 / 16.65, cfg 3 26.50 / 27.24 -- but cfg 1 (vector
@@ -824,12 +915,25 @@ class RSSMEngine:
         deter = g("obs.deter", (T, B, De))
         x3pre, x3 = g("obs.x3pre", (T, B, Hd)), g("obs.x3", (T, B, Hd))
         m3, r3 = g("obs.m3", (T, B)), g("obs.r3", (T, B))
-        post_logit = g("obs.post_logit", (T, B, S, D))
+        gauss, SW = self.gauss, self.SW
+        if gauss:
+            # dpost_logit = (dmean, dstd) [T,B,S] on the posterior's statistics (from the KL; either may be None);
+            # dprior_logit = (dmean, dstd, dstoch) on the prior's: folded through the prior head's activations here,
+            # for all steps at once
+            dpost_mean, dpost_std = dpost_logit
+            post_raw, post_eps = g("obs.post_raw", (T, B, SW)), g("obs.post_eps", (T, B, S))
+            dprior_logit_g = g("obs.dprior_raw", (T, B, SW))
+            ops.gauss_head_bwd(g("obs.prior_raw", (T, B, SW)), dprior_logit_g, dmean=dprior_logit[0],
+                               dstd=dprior_logit[1], dstoch=dprior_logit[2], eps=g("obs.prior_eps", (T, B, S)),
+                               **self._head_bwd_kw())
+            dprior_logit = dprior_logit_g
+        else:
+            post_logit = g("obs.post_logit", (T, B, S, D))
         x2pre, x2 = g("obs.x2pre", (T, B, Hd)), g("obs.x2", (T, B, Hd))
         m2, r2 = g("obs.m2", (T, B)), g("obs.r2", (T, B))
         # ---- prior head, batched: prior_logit -> ims -> LN/SiLU -> img_out -> deter
         dx2 = g("obs.dx2", (TB, Hd))
-        dpl2 = v2(dprior_logit, SD)
+        dpl2 = v2(dprior_logit, SW)
         side = SideStream(dprior_logit.device, lanes_pay=lanes_pay)
         ops.gemm(dpl2, P.ims.W, dx2, transB=False)
         dx2pre = g("obs.dx2pre", (TB, Hd))
@@ -856,14 +960,17 @@ class RSSMEngine:
             dx3pre = g("obs.dx3pre", (T, B, Hd))
             dgpre = g("obs.dgpre", (T, B, 3 * De))
             dx1pre = g("obs.dx1pre", (T, B, Hd))
-            fuse_carry = _FUSE_CARRY
+            fuse_carry = _FUSE_CARRY and not gauss  # (the fused carry launches end in the one-hot straight-through)
             # row operations in the prologue of the few-row GEMM that consumes them (csrc/scanops.hip): 5 launches per step
             fuse_row = (_FUSE_SCAN_ROW and _FUSE_SCAN_LNBWD and B <= 64 and ops.scan_lnbwd_gemm_ok(Hd, De)
                         and ops.scan_lnbwd_gemm_ok(Hd, SD))
             fuse_cs = (_FUSE_SCAN_ROW and _FUSE_SCAN_CS and B <= 64 and fuse_carry and ops.scan_carry_st_gemm_ok(S, D, Hd))
             # (the fused first launch re-reads its inputs from every column tile: the finished logit gradient goes to its
             # own buffer instead of in place)
-            dpl_out = g("obs.dpl_out", (T, B, S, D)) if fuse_cs else dpost_logit
+            if gauss:
+                dpl_out = g("obs.dpost_raw", (T, B, SW))
+            else:
+                dpl_out = g("obs.dpl_out", (T, B, S, D)) if fuse_cs else dpost_logit
             # (measured, world-model update: cfg 2 (De 512, 16 rows) 10.30 -> 10.15 ms; cfg 3 (De 1024, 32 rows) 17.19 -> 17.48:
             # 288 workgroups x 2 row blocks each re-reading 192 KB of factors -- the wide cell keeps its own launch)
             fuse_gru = (_FUSE_SCAN_ROW and _FUSE_SCAN_GRUBWD and B <= 32 and De <= 512
@@ -892,6 +999,14 @@ class RSSMEngine:
                     carry = None if t == T - 1 else (dsin[t + 1], dxd[t + 1][:, Hd:], first[t + 1], gd_t, dstoch0, ddeter0)
                     ops.scan_carry_st_gemm(gs_t.view(B, SD), post_logit[t], dpost_logit[t], dpl_out[t], P.obs.W, dx3[t],
                                            unimix=self.unimix, carry=carry)
+                elif gauss:
+                    # the sample's reparameterised path (gs_t: heads + the carry out of step t+1) and the KL's gradients
+                    # on mean / std through the head's activations, then dx3 += draw W_obs
+                    ops.gauss_head_bwd(post_raw[t], dpl_out[t], dstoch=gs_t,
+                                       dmean=None if dpost_mean is None else dpost_mean[t],
+                                       dstd=None if dpost_std is None else dpost_std[t], eps=post_eps[t],
+                                       **self._head_bwd_kw())
+                    ops.gemm(dpl_out[t], P.obs.W, dx3[t], transB=False, accumulate="atomic")
                 else:
                     if t == T - 1 or not fuse_carry:  # (otherwise done by step t+1's fused carry + straight-through launch)
                         ops.onehot_st_bwd(post_logit[t], gs_t.view(B, S, D), dpost_logit[t], unimix=self.unimix,
@@ -928,7 +1043,7 @@ class RSSMEngine:
             # ---- the encoder-output gradient (critical path) and, beside it, the batched weight gradients
         side.join()  # the init-state backward below adds into the same prior-head gradients
         ops.gemm(v2(dx3pre, Hd), P.obs_out.W[:, De:], v2(dembed, E), transB=False)
-        dpl = v2(dpl_out, SD)
+        dpl = v2(dpl_out, SW)
 
         def _scan_wgrads():
             # (one grid for these products, ops.gemm_group in SideStream.run; the init-state backward's additions into the
@@ -978,12 +1093,18 @@ class RSSMEngine:
         ops.gru_fwd(bufs["gpre"], P.gru.g, P.gru.b, deter, bufs["deter"], bufs["mg"], bufs["rg"])
         if not head:
             return
-        fuse_smp = _FUSE_SAMPLE and ops.gemm_sample_ok(M, self.SD, self.D)
+        fuse_smp = _FUSE_SAMPLE and not self.gauss and ops.gemm_sample_ok(M, self.SD, self.D)
         if wcat is not None:
             ops.gemm(bufs["deter"], wcat, bufs["cat"])
         else:
             ops.gemm(bufs["deter"], P.img_out.W, bufs["x2pre"])
         ops.ln_act_fwd(bufs["x2pre"], P.img_out.g, P.img_out.b, bufs["x2"], bufs["m2"], bufs["r2"], act=True)
+        if self.gauss:
+            # bufs: raw [M,2S], mean / std / stoch / eps [M,S]; noise: N(0,1) draws [M,S]
+            ops.gemm(bufs["x2"], P.ims.W, bufs["raw"], bias=P.ims.b)
+            ops.gauss_head_fwd(bufs["raw"], bufs["stoch"], bufs["mean"], bufs["std"], eps=noise, rng=rng,
+                               eps_out=bufs["eps"], mode=not sample, **self.head)
+            return
         io = None if idx_out is None else idx_out.view(-1)
         if fuse_smp:
             ops.gemm_sample(bufs["x2"], P.ims.W, bufs["logit"].view(M, self.SD), bufs["stoch"], bias=P.ims.b,
@@ -1018,8 +1139,11 @@ class RSSMEngine:
         P = self.P
         M = dstoch.shape[0]
         S, D, SD, De, Hd = self.S, self.D, self.SD, self.De, self.Hd
-        dlogit = scratch["dlogit"]
-        ops.onehot_st_bwd(bufs["logit"], dstoch.view(M, S, D), dlogit.view(M, S, D), unimix=self.unimix)
+        dlogit = scratch["dlogit"]  # [M, SW]
+        if self.gauss:
+            ops.gauss_head_bwd(bufs["raw"], dlogit, dstoch=dstoch, eps=bufs["eps"], **self._head_bwd_kw())
+        else:
+            ops.onehot_st_bwd(bufs["logit"], dstoch.view(M, S, D), dlogit.view(M, S, D), unimix=self.unimix)
         if wt is not None:  # transposed weights (pack_bwd): every data gradient in the y = x B^T form
             ops.gemm(dlogit, wt["ims"], scratch["dx2"])
             dense_ln_bwd_pre(P.img_out, scratch["dx2"], bufs["x2pre"], bufs["m2"], bufs["r2"], scratch["dx2pre"],

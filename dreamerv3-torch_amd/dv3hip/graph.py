@@ -960,6 +960,19 @@ class PolicyRunner:
         self._buckets = weight_buckets(agent)
         self._weights = None
 
+    @staticmethod
+    def _state_layout(dyn, n):
+        """(key, shape) of the carried latent in the packed step buffer, behind [action | logprob]: stoch | deter | logit
+        for categorical latents, stoch | deter | mean | std for continuous ones (dyn_discrete: 0)."""
+        S, D, De = dyn._stoch, dyn._discrete, dyn._deter
+        if not D:
+            return [("stoch", (n, S)), ("deter", (n, De)), ("mean", (n, S)), ("std", (n, S))]
+        return [("stoch", (n, S, D)), ("deter", (n, De)), ("logit", (n, S, D))]
+
+    @staticmethod
+    def _state_views(flat, offs, layout):
+        return {k: flat[offs[2 + i]:offs[3 + i]].view(shp) for i, (k, shp) in enumerate(layout)}
+
     def _weights_where(self):
         return tuple((b.flat.data_ptr(), b.settled()) if b.flat is not None else (0, False) for b in self._buckets)
 
@@ -968,8 +981,9 @@ class PolicyRunner:
         dyn = ag._wm.dynamics
         dev = torch.device(ag._config.device)
         n = len(obs["is_first"])
-        S, D, De, A = dyn._stoch, dyn._discrete, dyn._deter, dyn._num_actions
-        st = dict(obs={}, pin={})
+        A = dyn._num_actions
+        layout = self._state_layout(dyn, n)
+        st = dict(obs={}, pin={}, layout=layout)
         for k, v in obs.items():
             t = torch.as_tensor(v)
             dt = torch.uint8 if (k == "image" and t.dtype == torch.uint8) else torch.float32
@@ -979,10 +993,11 @@ class PolicyRunner:
         # and a pool of spinning OpenMP workers is what an env loop under a CPU quota cannot afford (r04: one acting
         # step in twelve took ~100 ms, the cgroup's throttling period; 0.29 ms median either way)
         st["pin_np"] = {k: v.numpy() for k, v in st["pin"].items()}
-        # one flat buffer holds the step's outputs [action | logprob | stoch | deter | logit]; the carried state the
+        # one flat buffer holds the step's outputs [action | logprob | stoch | deter | logit] (continuous latents:
+        # [action | logprob | stoch | deter | mean | std]); the carried state the
         # graph READS is the same memory (views of the previous step's outputs): when the caller hands back exactly
         # what the last step returned, nothing has to be copied in (see _load)
-        sizes = [n * A, n, n * S * D, n * De, n * S * D]
+        sizes = [n * A, n] + [int(np.prod(shp)) for _, shp in layout]
         st["packed"] = torch.zeros(sum(sizes), device=dev)
         st["sizes"] = sizes
         offs = [0]
@@ -990,14 +1005,13 @@ class PolicyRunner:
             offs.append(offs[-1] + sz)
         pk = st["packed"]
         st["action"] = pk[offs[0]:offs[1]].view(n, A)
-        st["state"] = {"stoch": pk[offs[2]:offs[3]].view(n, S, D), "deter": pk[offs[3]:offs[4]].view(n, De),
-                       "logit": pk[offs[4]:offs[5]].view(n, S, D)}
+        st["state"] = self._state_views(pk, offs, layout)
         st["offs"] = offs
 
         def core():
             out, (latent, action) = ag._policy_eager(st["obs"], (st["state"], st["action"]), training)
             # every read of the carried state precedes this launch in stream order
-            ops.concat_flat([out["action"], out["logprob"].reshape(-1), latent["stoch"], latent["deter"], latent["logit"]],
+            ops.concat_flat([out["action"], out["logprob"].reshape(-1)] + [latent[k].contiguous() for k, _ in layout],
                             st["packed"])
 
         self._load(st, obs, state)
@@ -1033,7 +1047,7 @@ class PolicyRunner:
             st["action"].zero_()
         elif not PolicyRunner._is_last_output(st, state):
             latent, action = state
-            for k in ("stoch", "deter", "logit"):
+            for k, _ in st["layout"]:
                 st["state"][k].copy_(latent[k], non_blocking=True)
             st["action"].copy_(action, non_blocking=True)
 
@@ -1048,8 +1062,7 @@ class PolicyRunner:
         flat, version = last
         latent, action = state
         offs = st["offs"]
-        want = ((action, offs[0]), (latent.get("stoch"), offs[2]), (latent.get("deter"), offs[3]),
-                (latent.get("logit"), offs[4]))
+        want = ((action, offs[0]),) + tuple((latent.get(k), offs[2 + i]) for i, (k, _) in enumerate(st["layout"]))
         for t, off in want:
             if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous():
                 return False
@@ -1082,10 +1095,8 @@ class PolicyRunner:
         st["graph"].replay()
         flat = st["packed"].clone()
         st["last"] = (flat, flat._version)
-        dyn = self.agent._wm.dynamics
-        S, D, De, A = dyn._stoch, dyn._discrete, dyn._deter, dyn._num_actions
+        A = self.agent._wm.dynamics._num_actions
         o = st["offs"]
         action, logprob = flat[o[0]:o[1]].view(n, A), flat[o[1]:o[2]].view(n)
-        latent = {"stoch": flat[o[2]:o[3]].view(n, S, D), "deter": flat[o[3]:o[4]].view(n, De),
-                  "logit": flat[o[4]:o[5]].view(n, S, D)}
+        latent = self._state_views(flat, o, st["layout"])
         return {"action": action, "logprob": logprob}, (latent, action)

@@ -951,6 +951,132 @@ def kl_bwd(post_logit, prior_logit, kl, dpost, dprior, *, unimix, free, dyn_scal
           int(acc_prior), _stream())
 
 
+GAUSS_MEAN_ACTS = {"none": 0, "tanh5": 1}
+# "identity": the input already is a standard deviation (tools.NormalLatent samples from {mean, std} with it)
+GAUSS_STD_ACTS = {"softplus": 0, "abs": 1, "sigmoid": 2, "sigmoid2": 3, "identity": 4}
+GAUSS_MAX_S = 1024
+
+
+def _gauss_acts(mean_act, std_act):
+    if mean_act not in GAUSS_MEAN_ACTS:
+        raise NotImplementedError(f"mean_act {mean_act!r}: one of {sorted(GAUSS_MEAN_ACTS)}")
+    if std_act not in GAUSS_STD_ACTS:
+        raise NotImplementedError(f"std_act {std_act!r}: one of {sorted(GAUSS_STD_ACTS)}")
+    return GAUSS_MEAN_ACTS[mean_act], GAUSS_STD_ACTS[std_act]
+
+
+def _gauss_rows(raw, name):
+    """raw [..., 2S] contiguous -> (M, S)."""
+    _contig(raw, name)
+    S2 = raw.shape[-1] if raw.dim() else 0
+    if S2 < 2 or S2 % 2 or S2 // 2 > GAUSS_MAX_S:
+        raise ValueError(f"{name}: last dim must be 2*S with 1 <= S <= {GAUSS_MAX_S}, got shape {tuple(raw.shape)}")
+    return raw.numel() // S2, S2 // 2
+
+
+def _gauss_like(t, name, M, S):
+    if t is not None:
+        _contig(t, name)
+        if t.numel() != M * S or (M and t.shape[-1] != S):
+            raise ValueError(f"{name}: expected [..., {S}] with {M} rows, got shape {tuple(t.shape)}")
+
+
+def gauss_head_fwd(raw, stoch, mean=None, std=None, *, eps=None, rng=None, eps_out=None, mean_act="none",
+                   std_act="softplus", min_std=0.1, mode=False, next_blend=None):
+    """raw [..., 2S] (mean_raw | std_raw) -> mean, std, stoch = mean + std * eps, each [..., S].  eps: given N(0,1)
+    draws, or the Philox draws fill_normal would make on an [M, S] array at this position of `rng` (eps_out receives
+    them).  mode: stoch = mean.  next_blend = (next_first [M], init [S], next_out [M, S]): also write the next
+    observe step's reset blend of the sample."""
+    M, S = _gauss_rows(raw, "raw")
+    ma, sa = _gauss_acts(mean_act, std_act)
+    for t, nm in ((stoch, "stoch"), (mean, "mean"), (std, "std"), (eps, "eps"), (eps_out, "eps_out")):
+        _gauss_like(t, nm, M, S)
+    if stoch is None:
+        raise ValueError("stoch: output required")
+    rng_state, rng_off = None, 0
+    if not mode and eps is None:
+        if rng is None:
+            raise ValueError("sampling needs eps or an RngStream")
+        rng_state, rng_off = rng.state, rng.take(M * S)
+    nf = init = nout = None
+    if next_blend is not None:
+        nf, init, nout = next_blend
+        _contig(nf, "next_first"), _contig(init, "init")
+        _gauss_like(nout, "next_out", M, S)
+        if nf.numel() != M or init.numel() != S:
+            raise ValueError("next_blend shapes mismatch")
+    n = M * S
+    _call("dv3_gauss_head_fwd", _ptr(raw), _ptr(eps), _ptr(rng_state), int(rng_off), _ptr(eps_out), _ptr(mean),
+          _ptr(std), _ptr(stoch), M, S, ma, sa, float(min_std), int(bool(mode)), _ptr(nf), _ptr(init), _ptr(nout),
+          _stream(), flops=12.0 * n,
+          nbytes=4.0 * n * (3 + (mean is not None) + (std is not None) + (eps is not None or eps_out is not None)
+                            + (nout is not None)))
+    return stoch
+
+
+def gauss_head_bwd(raw, draw, *, dstoch=None, dmean=None, dstd=None, eps=None, mean_act="none", std_act="softplus",
+                   mode=False, accumulate=False):
+    """draw [..., 2S] (+)= {(dstoch + dmean) mean_act', (dstoch * eps + dstd) std_act'}; mode: no eps term."""
+    M, S = _gauss_rows(raw, "raw")
+    ma, sa = _gauss_acts(mean_act, std_act)
+    if _gauss_rows(draw, "draw") != (M, S):
+        raise ValueError("draw shape mismatch")
+    for t, nm in ((dstoch, "dstoch"), (dmean, "dmean"), (dstd, "dstd"), (eps, "eps")):
+        _gauss_like(t, nm, M, S)
+    if not mode and dstoch is not None and eps is None:
+        raise ValueError("the sample's backward needs the eps of its forward")
+    n = M * S
+    ins = sum(t is not None for t in (dstoch, dmean, dstd, eps))
+    _call("dv3_gauss_head_bwd", _ptr(dstoch), _ptr(dmean), _ptr(dstd), _ptr(raw), _ptr(eps), _ptr(draw), M, S, ma, sa,
+          int(bool(mode)), int(bool(accumulate)), _stream(), flops=12.0 * n,
+          nbytes=4.0 * n * (ins + 4 + 2 * bool(accumulate)))
+    return draw
+
+
+def _gauss_kl_args(post_mean, post_std, prior_mean, prior_std, kl):
+    S = post_mean.shape[-1] if post_mean.dim() else 0
+    if S < 1 or S > GAUSS_MAX_S:
+        raise ValueError(f"post_mean: last dim S must be in [1, {GAUSS_MAX_S}]")
+    _contig(post_mean, "post_mean")
+    R = post_mean.numel() // S
+    for t, nm in ((post_std, "post_std"), (prior_mean, "prior_mean"), (prior_std, "prior_std")):
+        if t is None:
+            raise ValueError(nm + ": required")
+        _gauss_like(t, nm, R, S)
+    _contig(kl, "kl")
+    if kl.numel() != R:
+        raise ValueError("kl size mismatch")
+    return R, S
+
+
+def gauss_kl_fwd(post_mean, post_std, prior_mean, prior_std, kl, ent_post=None, ent_prior=None):
+    """kl [R] = KL(N(post) || N(prior)) summed over S; ent_* [R] (optional): the two entropies."""
+    R, S = _gauss_kl_args(post_mean, post_std, prior_mean, prior_std, kl)
+    for t, nm in ((ent_post, "ent_post"), (ent_prior, "ent_prior")):
+        if t is not None:
+            _contig(t, nm)
+            if t.numel() != R:
+                raise ValueError(nm + " size mismatch")
+    _call("dv3_gauss_kl_fwd", _ptr(post_mean), _ptr(post_std), _ptr(prior_mean), _ptr(prior_std), _ptr(kl),
+          _ptr(ent_post), _ptr(ent_prior), R, S, _stream(), flops=14.0 * R * S, nbytes=16.0 * R * S + 12.0 * R)
+
+
+def gauss_kl_bwd(post_mean, post_std, prior_mean, prior_std, kl, *, dpost_mean=None, dpost_std=None, dprior_mean=None,
+                 dprior_std=None, free, dyn_scale, rep_scale, upstream, acc_post=False, acc_prior=False):
+    R, S = _gauss_kl_args(post_mean, post_std, prior_mean, prior_std, kl)
+    outs = ((dpost_mean, "dpost_mean"), (dpost_std, "dpost_std"), (dprior_mean, "dprior_mean"),
+            (dprior_std, "dprior_std"))
+    if all(t is None for t, _ in outs):
+        raise ValueError("gauss_kl_bwd: no output given")
+    for t, nm in outs:
+        _gauss_like(t, nm, R, S)
+    n_out = sum(t is not None for t, _ in outs)
+    _call("dv3_gauss_kl_bwd", _ptr(post_mean), _ptr(post_std), _ptr(prior_mean), _ptr(prior_std), _ptr(kl),
+          _ptr(dpost_mean), _ptr(dpost_std), _ptr(dprior_mean), _ptr(dprior_std), R, S, float(free), float(dyn_scale),
+          float(rep_scale), float(upstream), int(bool(acc_post)), int(bool(acc_prior)), _stream(),
+          flops=16.0 * R * S, nbytes=4.0 * R * S * (4 + n_out) + 4.0 * R)
+
+
 def _disc_rows(logits):
     _contig(logits, "logits")
     if logits.shape[-1] != 255:

@@ -63,6 +63,16 @@ SHAPES = {
     "cfg5_b4": dict(stoch=32, discrete=32, deter=2048, hidden=1024, units=1024, A=17, cnn_depth=96, B=4, T=8, H=5,
                     actor_dist="onehot", imag_gradient="reinforce", encoder="cnn", actor_layers=5, reward_layers=5,
                     cont_layers=5),
+    # continuous Gaussian latents (dyn_discrete: 0; networks.py:87-91, 251-270): the state is `stoch` wide, the stat
+    # layers 2 * stoch.  Optional keys mean_act / std_act / min_std -> dyn_mean_act / dyn_std_act / dyn_min_std
+    # (default: the configs.yaml values, none / sigmoid2 / 0.1)
+    "tiny_gauss": dict(stoch=8, discrete=0, deter=16, hidden=16, units=16, A=3, cnn_depth=2, B=3, T=6, H=4,
+                       actor_dist="normal", imag_gradient="dynamics", encoder="cnn"),
+    "tiny_gauss_onehot": dict(stoch=8, discrete=0, deter=16, hidden=16, units=16, A=5, cnn_depth=2, B=3, T=6, H=4,
+                              actor_dist="onehot", imag_gradient="reinforce", encoder="cnn", mean_act="tanh5",
+                              std_act="softplus"),
+    "cfg2_gauss": dict(stoch=32, discrete=0, deter=512, hidden=512, units=512, A=6, cnn_depth=32, B=16, T=64, H=15,
+                       actor_dist="normal", imag_gradient="dynamics", encoder="cnn"),
 }
 # walker_walk proprio keys, in the order the reference's obs_space dict would list them
 PROPRIO_KEYS: Tuple[Tuple[str, int], ...] = (("orientations", 14), ("height", 1), ("velocity", 9))
@@ -96,6 +106,9 @@ def make_config(name, device="cuda:0"):
                dyn_deter=s["deter"], dyn_hidden=s["hidden"], units=s["units"], batch_size=s["B"],
                batch_length=s["T"], imag_horizon=s["H"], imag_gradient=s["imag_gradient"],
                imag_gradient_mix=s.get("imag_gradient_mix", 0.0))
+    for key in ("mean_act", "std_act", "min_std"):
+        if key in s:
+            cfg["dyn_" + key] = s[key]
     cfg["encoder"]["cnn_depth"] = s["cnn_depth"]
     cfg["decoder"]["cnn_depth"] = s["cnn_depth"]
     if s["actor_dist"] == "onehot":

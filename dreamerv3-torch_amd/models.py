@@ -114,7 +114,7 @@ class WorldModel(nn.Module):
                                       config.dyn_std_act, config.dyn_min_std, config.unimix_ratio, config.initial,
                                       config.num_actions, self.embed_size, config.device)
         self.heads = nn.ModuleDict()
-        feat_size = config.dyn_stoch * config.dyn_discrete + config.dyn_deter
+        feat_size = config.dyn_stoch * (config.dyn_discrete or 1) + config.dyn_deter
         self.heads["decoder"] = networks.MultiDecoder(feat_size, shapes, **config.decoder)
         self.heads["reward"] = networks.MLP(
             feat_size, (255,) if config.reward_head["dist"] == "symlog_disc" else (), config.reward_head["layers"],
@@ -213,7 +213,8 @@ class WorldModel(nn.Module):
         dyn = self.dynamics
         rssm = dyn.engine
         ws = rssm.ws
-        S, D, SD, De = dyn._stoch, dyn._discrete, dyn._stoch * dyn._discrete, dyn._deter
+        S, D, SD, De = dyn._stoch, dyn._discrete, dyn._stoch * (dyn._discrete or 1), dyn._deter
+        gauss = not D  # continuous latents: mean / std in place of the logits, csrc/gaussops.hip in place of catops
         nz = noise or {}
         rng = dyn._rng()
         self._model_opt.begin()
@@ -267,7 +268,10 @@ class WorldModel(nn.Module):
         ps, dt = out["post_stoch"].view(TB, SD), out["deter"].view(TB, De)
         kl = ws.get("wm.kl", (T, B))
         ent_p, ent_q = ws.get("wm.ent_post", (T, B)), ws.get("wm.ent_prior", (T, B))
-        ops.kl_fwd(out["post_logit"], out["prior_logit"], kl, ent_p, ent_q, unimix=dyn._unimix_ratio)
+        if gauss:
+            ops.gauss_kl_fwd(out["post_mean"], out["post_std"], out["prior_mean"], out["prior_std"], kl, ent_p, ent_q)
+        else:
+            ops.kl_fwd(out["post_logit"], out["prior_logit"], kl, ent_p, ent_q, unimix=dyn._unimix_ratio)
         # the reverse scan beside the deferred weight gradients on two CU-masked streams, where that pays
         lanes_pay = rssm.lanes_pay(heavy_side=bool(self.heads["decoder"].cnn_shapes))
         E.SideStream.host_sync_point(lanes_pay)  # (captured update: the lanes are launched once the GPU is here)
@@ -320,7 +324,7 @@ class WorldModel(nn.Module):
         if not wrote:
             gs.zero_(), gd.zero_()
         # reward head: -log_prob(reward) under the 255-bucket two-hot head
-        pidx = out["post_idx"].view(TB, S) if E._GATHER_OBS else None
+        pidx = out["post_idx"].view(TB, S) if E._GATHER_OBS and not gauss else None
         reng = self.heads["reward"].engine_for(".wm")
         if pidx is not None:
             reng.pack_onehot(SD)
@@ -349,9 +353,18 @@ class WorldModel(nn.Module):
         ceng.backward(ps, dt, slice(0, TB), dout=dc, wgrad=True, dx1=gs.view(TB, SD) if g_c else None,
                       dx2=gd.view(TB, De) if g_c else None, acc_dx=True, defer=deferred)
         # KL
-        dpl, dql = ws.get("wm.dpost_logit", (T, B, S, D)), ws.get("wm.dprior_logit", (T, B, S, D))
-        ops.kl_bwd(out["post_logit"], out["prior_logit"], kl, dpl, dql, unimix=dyn._unimix_ratio, free=cfg.kl_free,
-                   dyn_scale=cfg.dyn_scale, rep_scale=cfg.rep_scale, upstream=up)
+        if gauss:
+            # gradients on the four statistics; the scan's backward folds them through the heads' activations
+            dpm, dps, dqm, dqs = (ws.get(f"wm.d{nm}", (T, B, S)) for nm in ("post_mean", "post_std", "prior_mean",
+                                                                            "prior_std"))
+            ops.gauss_kl_bwd(out["post_mean"], out["post_std"], out["prior_mean"], out["prior_std"], kl, dpost_mean=dpm,
+                             dpost_std=dps, dprior_mean=dqm, dprior_std=dqs, free=cfg.kl_free, dyn_scale=cfg.dyn_scale,
+                             rep_scale=cfg.rep_scale, upstream=up)
+            dpl, dql = (dpm, dps), (dqm, dqs, None)
+        else:
+            dpl, dql = ws.get("wm.dpost_logit", (T, B, S, D)), ws.get("wm.dprior_logit", (T, B, S, D))
+            ops.kl_bwd(out["post_logit"], out["prior_logit"], kl, dpl, dql, unimix=dyn._unimix_ratio, free=cfg.kl_free,
+                       dyn_scale=cfg.dyn_scale, rep_scale=cfg.rep_scale, upstream=up)
         ops.dot_accumulate(kl.view(TB), acc[4:5], clip_min=cfg.kl_free, scale=up)  # mean of the clipped KL
         # ---- backward through the scan and the encoder
         dembed = ws.get("wm.dembed", (T, B, E_))
@@ -388,7 +401,11 @@ class WorldModel(nn.Module):
                        rep_scale=cfg.rep_scale, dyn_loss=acc[4], rep_loss=acc[4], kl=ws.get("wm.kl_mean", (1,))[0],
                        prior_ent=acc[5], post_ent=acc[6])
         bt = lambda x: x.transpose(0, 1)
-        post = {"stoch": bt(out["post_stoch"]), "deter": bt(out["deter"]), "logit": bt(out["post_logit"])}
+        if gauss:
+            post = {"stoch": bt(out["post_stoch"]), "deter": bt(out["deter"]), "mean": bt(out["post_mean"]),
+                    "std": bt(out["post_std"])}
+        else:
+            post = {"stoch": bt(out["post_stoch"]), "deter": bt(out["deter"]), "logit": bt(out["post_logit"])}
         self._last = dict(out=out, embed=embed.view(T, B, E_), kl=kl, ent_post=ent_p, action_tm=out["action"])
         context = _LazyContext(self, post)
         rng.commit()
@@ -442,7 +459,7 @@ class ImagBehavior(nn.Module):
         super().__init__()
         self._config = config
         self._world_model = world_model
-        feat_size = config.dyn_stoch * config.dyn_discrete + config.dyn_deter
+        feat_size = config.dyn_stoch * (config.dyn_discrete or 1) + config.dyn_deter
         self.actor = networks.MLP(
             feat_size, (config.num_actions,), config.actor["layers"], config.units, config.act, config.norm,
             config.actor["dist"], config.actor["std"], config.actor["min_std"], config.actor["max_std"], absmax=1.0,
@@ -491,11 +508,14 @@ class ImagBehavior(nn.Module):
         return b.ensure()
 
     def _flat_start(self, start):
-        """start {[B,T,...]} -> ([N,SD], [N,De], [N,SD]) without a copy when it is a time-major view."""
+        """start {[B,T,...]} -> ([N,SD], [N,De], [N,SD]) without a copy when it is a time-major view (continuous
+        latents: stoch, deter, mean, std)."""
         dyn = self._world_model.dynamics
-        SD = dyn._stoch * dyn._discrete
+        SD = dyn._stoch * (dyn._discrete or 1)
         outs = []
-        for k, w in (("stoch", SD), ("deter", dyn._deter), ("logit", SD)):
+        keys = (("stoch", SD), ("deter", dyn._deter), ("logit", SD)) if dyn._discrete else \
+            (("stoch", SD), ("deter", dyn._deter), ("mean", SD), ("std", SD))
+        for k, w in keys:
             v = start[k]
             tm = v.transpose(0, 1)
             src = tm if tm.is_contiguous() else v.contiguous()
@@ -511,8 +531,11 @@ class ImagBehavior(nn.Module):
         st = self._im
         S, D = self._world_model.dynamics._stoch, self._world_model.dynamics._discrete
         H, N = st["H"], st["N"]
-        states = {"stoch": st["stoch"].view(H, N, S, D).clone(), "deter": st["deter"].clone(),
-                  "logit": st["logit"].view(H, N, S, D).clone()}
+        if not D:
+            states = {k: v.clone() for k, v in self._imag_state(st).items()}
+        else:
+            states = {"stoch": st["stoch"].view(H, N, S, D).clone(), "deter": st["deter"].clone(),
+                      "logit": st["logit"].view(H, N, S, D).clone()}
         feats = torch.cat([st["stoch"], st["deter"]], -1)
         return feats, states, st["action"].clone()
 
@@ -538,22 +561,33 @@ class ImagBehavior(nn.Module):
         dyn = self._world_model.dynamics
         rssm = dyn.engine
         ws = rssm.ws
-        S, D, SD, De, Hd, A = dyn._stoch, dyn._discrete, dyn._stoch * dyn._discrete, dyn._deter, dyn._hidden, \
+        S, D, SD, De, Hd, A = dyn._stoch, dyn._discrete, dyn._stoch * (dyn._discrete or 1), dyn._deter, dyn._hidden, \
             dyn._num_actions
-        s0, d0, l0 = self._flat_start(start)
+        gauss = not D
+        flat = self._flat_start(start)
+        s0, d0 = flat[0], flat[1]
         N, H = s0.shape[0], horizon
         nz = noise or {}
         rng = dyn._rng()
         g = ws.get
-        stoch, deter, logit = g("im.stoch", (H, N, SD)), g("im.deter", (H, N, De)), g("im.logit", (H, N, SD))
-        stoch[0].copy_(s0), deter[0].copy_(d0), logit[0].copy_(l0)
+        stoch, deter = g("im.stoch", (H, N, SD)), g("im.deter", (H, N, De))
+        stoch[0].copy_(s0), deter[0].copy_(d0)
+        if gauss:
+            # states carry mean / std; raw (the prior head's output) and eps_s (its draws) are kept for the reverse rollout
+            logit = None
+            mean, std = g("im.mean", (H, N, SD)), g("im.std", (H, N, SD))
+            raw, eps_s = g("im.raw", (H, N, 2 * SD)), g("im.eps_s", (H, N, SD))
+            mean[0].copy_(flat[2]), std[0].copy_(flat[3])
+        else:
+            logit = g("im.logit", (H, N, SD))
+            logit[0].copy_(flat[2])
         action, ent = g("im.action", (H, N, A)), g("im.ent", (H, N))
         eps = g("im.eps", (H, N, A))
         actor_eng = self.actor.engine_for(".imag")
         U0 = actor_eng.P.layers[0].W.shape[0]
         # img_out and the dense half of the actor's first layer both read the new deter: one stacked GEMM per step
         # writes [x2pre | actor pre0 of the NEXT step] (engine.RSSMEngine.img_step_fwd, wcat)
-        stack = _FUSED_IMAG and _STACK_DETER
+        stack = _FUSED_IMAG and _STACK_DETER and not gauss  # (the stacked GEMM feeds the one-hot gather's base)
         cat = g("im.cat", (H, N, Hd + U0)) if stack else None
         step = dict(x1pre=g("im.x1pre", (H, N, Hd)), m1=g("im.m1", (H, N)), r1=g("im.r1", (H, N)),
                     x1=g("im.x1", (H, N, Hd)), gpre=g("im.gpre", (H, N, 3 * De)), mg=g("im.mg", (H, N)),
@@ -571,12 +605,14 @@ class ImagBehavior(nn.Module):
         f_img, f_act, flips = nz.get("force_img"), nz.get("force_act"), nz.get("flips")  # parity tests
         # The stochastic state is an exact one-hot (tools.py:452-460): carry its class indices and let every Linear
         # that reads it (actor layer 0, img_in) gather weight columns instead of multiplying zeros (engine.py).
-        idx = g("im.idx", (H, N, S), torch.int32)
-        ops.onehot_to_idx(stoch[0].view(N, S, D), idx[0].view(-1))  # class indices of the start states
+        idx = None
+        if not gauss:
+            idx = g("im.idx", (H, N, S), torch.int32)
+            ops.onehot_to_idx(stoch[0].view(N, S, D), idx[0].view(-1))  # class indices of the start states
         # (pipelined capture, graph.UpdateRunner.step_pipelined: everything up to here reads the posterior of the world
         # model's scan and runs BEFORE the next update's scan overwrites it; the rollout below runs beside that scan)
         E.Cuts.mark("bh.A")
-        if _FUSED_IMAG and not packed:
+        if _FUSED_IMAG and not packed and not gauss:
             tr = []
             actor_eng.pack_onehot(SD, defer=tr)
             rssm.pack_img_in(defer=tr)
@@ -596,8 +632,9 @@ class ImagBehavior(nn.Module):
                         head.update(eps_out=eps[t][rc], min_std=cfg.actor["min_std"], max_std=cfg.actor["max_std"])
                     else:
                         head.update(unimix=cfg.actor["unimix_ratio"], forced=None if f_act is None else f_act[t][rc])
-                    actor_eng.forward(stoch[t][rc], deter[t][rc], row0=t * N + r0, total=H * N, idx=idx[t][rc], D=D,
-                                      head=head, base0=cat[t - 1][rc][:, Hd:] if (stack and t > 0) else None)
+                    actor_eng.forward(stoch[t][rc], deter[t][rc], row0=t * N + r0, total=H * N,
+                                      idx=None if gauss else idx[t][rc], D=D, head=head,
+                                      base0=cat[t - 1][rc][:, Hd:] if (stack and t > 0) else None)
                 else:  # one launch per op (development switch DV3_FUSED_IMAG=0: the r01 launch sequence, for A/B)
                     _, mean_raw, std_raw = actor_eng.forward(stoch[t][rc], deter[t][rc], row0=t * N + r0, total=H * N)
                     if normal:
@@ -614,6 +651,13 @@ class ImagBehavior(nn.Module):
                         ops.onehot_ent_logp_fwd(mean_raw, None, ent[t][rc], None, unimix=cfg.actor["unimix_ratio"])
                 if t < H - 1:
                     b = {k: v[t][rc] for k, v in step.items()}
+                    if gauss:
+                        # (raw / eps_s of the transition t -> t+1 are kept at t+1, beside the state they produced)
+                        b.update(deter=deter[t + 1][rc], stoch=stoch[t + 1][rc], mean=mean[t + 1][rc], std=std[t + 1][rc],
+                                 raw=raw[t + 1][rc], eps=eps_s[t + 1][rc])
+                        rssm.img_step_fwd(stoch[t][rc], deter[t][rc], action[t][rc], b,
+                                          noise=None if q_img is None else q_img[t][rc], rng=rng)
+                        continue
                     b.update(deter=deter[t + 1][rc], logit=logit[t + 1][rc].view(n, S, D),
                              stoch=stoch[t + 1][rc].view(n, S, D))
                     rssm.img_step_fwd(stoch[t][rc], deter[t][rc], action[t][rc], b,
@@ -625,6 +669,8 @@ class ImagBehavior(nn.Module):
         rng.commit()
         self._im = dict(H=H, N=N, stoch=stoch, deter=deter, logit=logit, action=action, ent=ent, eps=eps, step=step,
                         actor=actor_eng, idx=idx)
+        if gauss:
+            self._im.update(mean=mean, std=std, raw=raw, eps_s=eps_s)
 
     # ------------------------------------------------------------------------------------------
     @tools.on_config_device
@@ -673,6 +719,8 @@ class ImagBehavior(nn.Module):
     def _imag_state(self, im):
         S, D = self._world_model.dynamics._stoch, self._world_model.dynamics._discrete
         H, N = im["H"], im["N"]
+        if not D:
+            return {"stoch": im["stoch"], "deter": im["deter"], "mean": im["mean"], "std": im["std"]}
         return {"stoch": im["stoch"].view(H, N, S, D), "deter": im["deter"], "logit": im["logit"].view(H, N, S, D)}
 
     def _eval_objective(self, objective, im, need_grad):
@@ -684,7 +732,8 @@ class ImagBehavior(nn.Module):
         leaves = dict(stoch=st["stoch"].detach().requires_grad_(need_grad),
                       deter=st["deter"].detach().requires_grad_(need_grad),
                       action=im["action"].detach().requires_grad_(need_grad))
-        state = {"stoch": leaves["stoch"], "deter": leaves["deter"], "logit": st["logit"].detach()}
+        state = {k: v.detach() for k, v in st.items()}
+        state.update(stoch=leaves["stoch"], deter=leaves["deter"])
         with torch.enable_grad() if need_grad else torch.no_grad():
             # as in the reference, `feat` is detached (models.py:513-517 returns get_feat(state).detach()): gradients
             # reach the dynamics through `state` and `action` only
@@ -730,7 +779,8 @@ class ImagBehavior(nn.Module):
         dyn = wm.dynamics
         rssm = dyn.engine
         ws = rssm.ws
-        S, D, SD, De, A = dyn._stoch, dyn._discrete, dyn._stoch * dyn._discrete, dyn._deter, dyn._num_actions
+        S, D, SD, De, A = dyn._stoch, dyn._discrete, dyn._stoch * (dyn._discrete or 1), dyn._deter, dyn._num_actions
+        gauss = not D
         H = cfg.imag_horizon
         self._update_slow_target()
         self._actor_opt.begin()
@@ -746,14 +796,16 @@ class ImagBehavior(nn.Module):
             # the reverse rollout's data-gradient operands) in ONE launch: the world model is frozen from here on
             # (models.py:335) and the actor / critic step only after the backward below
             tr = []
-            self.actor.engine_for(".imag").pack_onehot(SD, defer=tr)
-            for e in (reng, ceng, veng, seng):
-                e.pack_onehot(SD, defer=tr)
+            if not gauss:
+                self.actor.engine_for(".imag").pack_onehot(SD, defer=tr)
+                for e in (reng, ceng, veng, seng):
+                    e.pack_onehot(SD, defer=tr)
             if cfg.imag_gradient in ("dynamics", "both"):
                 wt_bwd = rssm.pack_bwd(defer=tr)
-            else:
+            elif not gauss:
                 rssm.pack_img_in(defer=tr)
-            ops.transpose2d_many(tr)
+            if tr:
+                ops.transpose2d_many(tr)
         self._imagine_fwd(start, H, noise, packed=True)
         E.Cuts.mark("bh.B")
         im = self._im
@@ -764,7 +816,7 @@ class ImagBehavior(nn.Module):
         g = ws.get
         # ---- heads over all H*N imagined states
         # first layers read feat = [stoch | deter]: deter through the MFMA GEMM, the one-hot stoch as a gather
-        fidx = im["idx"].view(HN, S) if _FUSED_IMAG else None
+        fidx = im["idx"].view(HN, S) if _FUSED_IMAG and not gauss else None
         use_dyn = cfg.imag_gradient in ("dynamics", "both")
         reward = g("bh.reward", (H, N))
         custom = objective is not None and self.__dict__.get("_objective_kinds", {}).get(
@@ -870,7 +922,7 @@ class ImagBehavior(nn.Module):
             ceng.backward(fs[rows], fd[rows], rows, dout=dcl.view(HN, 1)[rows], wgrad=False,
                           dx1=gs.view(HN, SD)[rows], dx2=gd.view(HN, De)[rows], acc_dx=True)
             Hd = dyn._hidden
-            scratch = dict(dlogit=g("bh.s.dlogit", (N, SD)), dx2=g("bh.s.dx2", (N, Hd)), dx2pre=g("bh.s.dx2pre", (N, Hd)),
+            scratch = dict(dlogit=g("bh.s.dlogit", (N, rssm.SW)), dx2=g("bh.s.dx2", (N, Hd)), dx2pre=g("bh.s.dx2pre", (N, Hd)),
                            dgpre=g("bh.s.dgpre", (N, 3 * De)), dx1=g("bh.s.dx1", (N, Hd)),
                            dx1pre=g("bh.s.dx1pre", (N, Hd)))
             E.Cuts.mark("bh.C")  # the reverse rollout: a chain of dependent 1024-row launches
@@ -878,7 +930,10 @@ class ImagBehavior(nn.Module):
                 if t < H - 1:
                     E.Cuts.mark(f"bh.C@{t}")
                 b = {k: v[t - 1] for k, v in im["step"].items()}
-                b.update(logit=im["logit"][t].view(N, S, D))
+                if gauss:
+                    b.update(raw=im["raw"][t], eps=im["eps_s"][t])
+                else:
+                    b.update(logit=im["logit"][t].view(N, S, D))
                 # state gradients flow straight into gs/gd[t-1] (which already hold the heads' gradient);
                 # step 0 is the detached start state: its slot is scratch
                 rssm.img_step_bwd(gs[t], gd[t], deter[t - 1], b, scratch, gs[t - 1], gd[t - 1], daction[t - 1],
@@ -924,7 +979,7 @@ class ImagBehavior(nn.Module):
         metrics["actor_entropy"] = acc[2]
         self.ema_to_wire()
         self._last = dict(reward=reward, value=value, target=target, weights=weights, disc=disc, slow=slow)
-        imag_state = {"stoch": stoch.view(H, N, S, D), "deter": deter, "logit": im["logit"].view(H, N, S, D)}
+        imag_state = self._imag_state(im)
         self._pending = ((None, imag_state, action, weights.view(H, N, 1)), metrics, (acc[0], acc[1]))
 
     def _actor_heads(self, im):

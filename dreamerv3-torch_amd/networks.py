@@ -13,7 +13,8 @@ Modules are parameter containers with the reference's names, shapes and state_di
   reference's surface with `loss.backward()` (exploration.Plan2Explore, the causal world models)
   run unchanged.
 
-Continuous latents (dyn_discrete: 0) are not implemented: no shipped config uses them.
+Continuous Gaussian latents (dyn_discrete: 0) run through the same two ways with csrc/gaussops.hip in place of the
+categorical kernels: states carry `mean` / `std` instead of `logit`, and the stochastic state is `stoch` wide.
 """
 from __future__ import annotations
 
@@ -102,27 +103,31 @@ class RSSM(nn.Module):
                  mean_act="none", std_act="softplus", min_std=0.1, unimix_ratio=0.01, initial="learned",
                  num_actions=None, embed=None, device=None):
         super().__init__()
+        discrete = int(discrete or 0)
         if not discrete:
-            raise NotImplementedError("continuous latents (dyn_discrete: 0) are not implemented")
+            ops._gauss_acts(mean_act, std_act)  # (raises for an activation the head kernel does not have)
         if act != "SiLU" or not norm or rec_depth != 1 or initial != "learned":
             raise NotImplementedError("kernels implement act=SiLU, norm=True, rec_depth=1, initial=learned")
         self._stoch, self._deter, self._hidden, self._discrete = stoch, deter, hidden, discrete
         self._unimix_ratio, self._num_actions, self._embed, self._device = unimix_ratio, num_actions, embed, device
         self._min_std, self._rec_depth, self._initial = min_std, rec_depth, initial
+        self._mean_act, self._std_act = mean_act, std_act
+        stoch_w = stoch * discrete if discrete else stoch  # width of the flattened stochastic state
+        stat_w = stoch * discrete if discrete else 2 * stoch  # logits, or mean_raw | std_raw (networks.py:80-91)
 
         def block(inp):
             seq = DenseLNBlock(inp, hidden)
             seq.apply(tools.weight_init)
             return seq
 
-        self._img_in_layers = block(stoch * discrete + num_actions)
+        self._img_in_layers = block(stoch_w + num_actions)
         self._cell = GRUCell(hidden, deter, norm=norm)
         self._cell.apply(tools.weight_init)
         self._img_out_layers = block(deter)
         self._obs_out_layers = block(deter + embed)
-        self._imgs_stat_layer = nn.Linear(hidden, stoch * discrete)
+        self._imgs_stat_layer = nn.Linear(hidden, stat_w)
         self._imgs_stat_layer.apply(tools.uniform_weight_init(1.0))
-        self._obs_stat_layer = nn.Linear(hidden, stoch * discrete)
+        self._obs_stat_layer = nn.Linear(hidden, stat_w)
         self._obs_stat_layer.apply(tools.uniform_weight_init(1.0))
         self.W = nn.Parameter(torch.zeros((1, deter), device=torch.device(device) if device else None),
                               requires_grad=True)
@@ -141,7 +146,7 @@ class RSSM(nn.Module):
         if eng is None or eng.ws is not ws:
             eng = E.RSSMEngine(self.params(), ws, stoch=self._stoch, discrete=self._discrete, deter=self._deter,
                                hidden=self._hidden, num_actions=self._num_actions, embed=self._embed,
-                               unimix=self._unimix_ratio)
+                               unimix=self._unimix_ratio, **self._head_kw())
             object.__setattr__(self, "_eng", eng)
         eng.P = self.params()
         return eng
@@ -149,12 +154,24 @@ class RSSM(nn.Module):
     def _rng(self):
         return tools.default_rng(self.W.device)
 
+    def _head_kw(self):
+        return dict(mean_act=self._mean_act, std_act=self._std_act, min_std=float(self._min_std))
+
     # ---- reference API (forward only) ------------------------------------------------------------
     def _all_params(self):
         return AG.rssm_param_list(self.params())
 
     def initial(self, batch_size):
         S, D = self._stoch, self._discrete
+        if not D:  # networks.py:111-117: mean / std zeros; stoch = the mean of the prior head at tanh(W)
+            if AG.wants_grad(*self._all_params()):
+                deter = AG.TanhFn.apply(self.W).repeat(batch_size, 1)
+                stoch = self.get_stoch(deter)
+            else:
+                s0, d0 = self.engine.init_state_fwd()
+                stoch, deter = s0.repeat(batch_size, 1), d0.repeat(batch_size, 1)
+            z = torch.zeros(batch_size, S, device=deter.device)
+            return dict(mean=z, std=z.clone(), stoch=stoch, deter=deter)
         if AG.wants_grad(*self._all_params()):  # networks.py:99-123: deter = tanh(W), stoch = mode of the prior head
             deter = AG.TanhFn.apply(self.W).repeat(batch_size, 1)
             return dict(logit=torch.zeros(batch_size, S, D, device=deter.device), stoch=self.get_stoch(deter),
@@ -165,14 +182,20 @@ class RSSM(nn.Module):
 
     def get_feat(self, state):
         st = state["stoch"]
+        if not self._discrete:
+            return torch.cat([st, state["deter"]], -1)
         return torch.cat([st.reshape(list(st.shape[:-2]) + [self._stoch * self._discrete]), state["deter"]], -1)
 
     def get_dist(self, state, dtype=None):
+        if not self._discrete:
+            return tools.NormalLatent(state["mean"], state["std"], rng=self._rng())
         return tools.IndependentOneHot(tools.OneHotDist(state["logit"], unimix_ratio=self._unimix_ratio,
                                                         rng=self._rng()))
 
     def get_stoch(self, deter):
         p = self.params()
+        if not self._discrete:
+            return self._suff_stats_layer("ims", self._img_out_layers(deter))["mean"]
         if AG.wants_grad(deter, *self._all_params()):
             x = self._img_out_layers(deter)
             logit = self._suff_stats_layer("ims", x)["logit"]
@@ -191,6 +214,8 @@ class RSSM(nn.Module):
         if lin is None:
             raise NotImplementedError(name)
         lead = x.shape[:-1]
+        if not self._discrete:  # networks.py:251-270 -> {"mean", "std"}, each [..., stoch]
+            return self._gauss_head(x, lin, mode=True)[0]
         if AG.wants_grad(x, lin.weight, lin.bias):
             out = AG.LinearFn.apply(x, lin.weight, lin.bias)
             return {"logit": out.reshape(tuple(lead) + (self._stoch, self._discrete))}
@@ -202,13 +227,44 @@ class RSSM(nn.Module):
     def _step_bufs(self, M, dev):
         S, D, De, Hd = self._stoch, self._discrete, self._deter, self._hidden
         mk = lambda *s: torch.empty(*s, device=dev)
+        if not D:
+            return dict(x1pre=mk(M, Hd), m1=mk(M), r1=mk(M), x1=mk(M, Hd), gpre=mk(M, 3 * De), mg=mk(M), rg=mk(M),
+                        deter=mk(M, De), x2pre=mk(M, Hd), m2=mk(M), r2=mk(M), x2=mk(M, Hd), raw=mk(M, 2 * S),
+                        mean=mk(M, S), std=mk(M, S), stoch=mk(M, S), eps=mk(M, S))
         return dict(x1pre=mk(M, Hd), m1=mk(M), r1=mk(M), x1=mk(M, Hd), gpre=mk(M, 3 * De), mg=mk(M), rg=mk(M),
                     deter=mk(M, De), x2pre=mk(M, Hd), m2=mk(M), r2=mk(M), x2=mk(M, Hd), logit=mk(M, S, D),
                     stoch=mk(M, S, D))
 
+    def _gauss_head(self, x, lin, *, mode, noise=None):
+        """Stat layer + its activations + the sample (or the mean) of the resulting Normal: x [..., hidden] ->
+        ({"mean", "std"}, stoch).  One GEMM and one dv3_gauss_head launch; with gradients, LinearFn + GaussHeadFn."""
+        S = self._stoch
+        lead = tuple(x.shape[:-1])
+        rng = None if (mode or noise is not None) else self._rng()
+        if AG.wants_grad(x, lin.weight, lin.bias):
+            raw = AG.LinearFn.apply(x, lin.weight, lin.bias)
+            mean, std, stoch = AG.GaussHeadFn.apply(raw, noise, rng, self._mean_act, self._std_act,
+                                                    float(self._min_std), bool(mode))
+        else:
+            x2 = x.to(torch.float32).reshape(-1, x.shape[-1]).contiguous()
+            raw = torch.empty(x2.shape[0], 2 * S, device=x.device)
+            ops.gemm(x2, lin.weight, raw, bias=lin.bias)
+            mean, std, stoch = (torch.empty(lead + (S,), device=x.device) for _ in range(3))
+            ops.gauss_head_fwd(raw, stoch, mean, std, eps=None if noise is None else noise.to(torch.float32).contiguous(),
+                               rng=rng, mode=mode, **self._head_kw())
+        if rng is not None:
+            rng.commit()
+        return {"mean": mean, "std": std}, stoch
+
     def _img_step_grad(self, prev_state, prev_action, sample, noise):
         """img_step as a chain of autograd nodes (each one a kernel pair): img_in -> GRU -> img_out -> stats -> sample."""
         st = prev_state["stoch"]
+        if not self._discrete:
+            x = self._img_in_layers(torch.cat([st, prev_action.to(torch.float32)], -1))
+            deter, _ = self._cell(x, [prev_state["deter"]])
+            stats, stoch = self._gauss_head(self._img_out_layers(deter), self._imgs_stat_layer, mode=not sample,
+                                            noise=noise)
+            return {"stoch": stoch, "deter": deter, **stats}
         x = torch.cat([st.reshape(tuple(st.shape[:-2]) + (self._stoch * self._discrete,)),
                        prev_action.to(torch.float32)], -1)
         x = self._img_in_layers(x)
@@ -229,6 +285,8 @@ class RSSM(nn.Module):
                                  prev_action.to(torch.float32).contiguous(), b, noise=noise,
                                  rng=self._rng(), sample=sample)
         self._rng().commit()
+        if not self._discrete:
+            return {"stoch": b["stoch"], "deter": b["deter"], "mean": b["mean"], "std": b["std"]}
         return {"stoch": b["stoch"], "deter": b["deter"], "logit": b["logit"]}
 
     def obs_step(self, prev_state, prev_action, embed, is_first, sample=True, noise=None, prior=True):
@@ -240,7 +298,7 @@ class RSSM(nn.Module):
         p = self.params()
         B = embed.shape[0]
         dev = embed.device
-        S, D, SD, De, Hd, A = self._stoch, self._discrete, self._stoch * self._discrete, self._deter, \
+        S, D, SD, De, Hd, A = self._stoch, self._discrete, self._stoch * (self._discrete or 1), self._deter, \
             self._hidden, self._num_actions
         ps = prev_state or {}
         if AG.wants_grad(embed, prev_action, ps.get("stoch"), ps.get("deter"), *self._all_params()):
@@ -256,6 +314,9 @@ class RSSM(nn.Module):
                 prev_state = {k: v * (1.0 - mm(v)) + init[k] * mm(v) for k, v in prev_state.items()}
             pri = self._img_step_grad(prev_state, prev_action, sample, nz.get("prior"))
             x = self._obs_out_layers(torch.cat([pri["deter"], embed.to(torch.float32)], -1))
+            if not D:
+                stats, stoch = self._gauss_head(x, self._obs_stat_layer, mode=not sample, noise=nz.get("post"))
+                return {"stoch": stoch, "deter": pri["deter"], **stats}, (pri if prior else None)
             logit = self._suff_stats_layer("obs", x)["logit"]
             dist = tools.OneHotDist(logit, unimix_ratio=self._unimix_ratio, rng=self._rng())
             stoch = dist.sample(noise=nz.get("post")) if sample else dist.mode()
@@ -275,9 +336,18 @@ class RSSM(nn.Module):
         nz = noise or {}
         b = self._step_bufs(B, dev)
         self.engine.img_step_fwd(sin, din, ain, b, noise=nz.get("prior"), rng=self._rng(), sample=sample, head=prior)
-        prior = {"stoch": b["stoch"], "deter": b["deter"], "logit": b["logit"]} if prior else None
         x3pre, x3 = torch.empty(B, Hd, device=dev), torch.empty(B, Hd, device=dev)
         E.dense_ln_fwd(p.obs_out, b["deter"], embed.contiguous(), x3pre, None, None, x3)
+        if not D:
+            prior = {"stoch": b["stoch"], "deter": b["deter"], "mean": b["mean"], "std": b["std"]} if prior else None
+            raw = torch.empty(B, 2 * S, device=dev)
+            ops.gemm(x3, p.obs.W, raw, bias=p.obs.b)
+            mean, std, stoch = (torch.empty(B, S, device=dev) for _ in range(3))
+            ops.gauss_head_fwd(raw, stoch, mean, std, eps=nz.get("post"), rng=self._rng(), mode=not sample,
+                               **self._head_kw())
+            self._rng().commit()
+            return {"stoch": stoch, "deter": b["deter"], "mean": mean, "std": std}, prior
+        prior = {"stoch": b["stoch"], "deter": b["deter"], "logit": b["logit"]} if prior else None
         logit = torch.empty(B, S, D, device=dev)
         ops.gemm(x3, p.obs.W, logit.view(B, SD), bias=p.obs.b)
         stoch = torch.empty(B, S, D, device=dev)
@@ -296,7 +366,15 @@ class RSSM(nn.Module):
             # the whole scan as ONE autograd node over engine.RSSMEngine.observe_fwd / observe_bwd
             tmg = lambda x: x.to(torch.float32).transpose(0, 1).contiguous()
             dims = dict(stoch=self._stoch, discrete=self._discrete, deter=self._deter, hidden=self._hidden,
-                        num_actions=self._num_actions, embed=self._embed, unimix=self._unimix_ratio)
+                        num_actions=self._num_actions, embed=self._embed, unimix=self._unimix_ratio, **self._head_kw())
+            if not self._discrete:
+                ps, pm, psd, dt, qs, qm, qsd = AG.ObserveGaussFn.apply(
+                    tmg(embed), tmg(action), tmg(is_first), nz.get("q_prior"), nz.get("q_post"), self._rng(), dims,
+                    *self._all_params())
+                self._rng().commit()
+                bt = lambda x: x.transpose(0, 1)
+                return ({"stoch": bt(ps), "deter": bt(dt), "mean": bt(pm), "std": bt(psd)},
+                        {"stoch": bt(qs), "deter": bt(dt), "mean": bt(qm), "std": bt(qsd)})
             ps, pl, dt, qs, ql = AG.ObserveFn.apply(tmg(embed), tmg(action), tmg(is_first), nz.get("q_prior"),
                                                    nz.get("q_post"), self._rng(), dims, *self._all_params())
             self._rng().commit()
@@ -319,13 +397,17 @@ class RSSM(nn.Module):
                                       q_post=nz.get("q_post"), rng=self._rng(), state0=state0)
         self._rng().commit()
         bt = lambda x: x.transpose(0, 1).clone()
+        if not self._discrete:
+            return tuple({"stoch": bt(out[k + "_stoch"]), "deter": bt(out["deter"]), "mean": bt(out[k + "_mean"]),
+                          "std": bt(out[k + "_std"])} for k in ("post", "prior"))
         post = {"stoch": bt(out["post_stoch"]), "deter": bt(out["deter"]), "logit": bt(out["post_logit"])}
         prior = {"stoch": bt(out["prior_stoch"]), "deter": bt(out["deter"]), "logit": bt(out["prior_logit"])}
         return post, prior
 
     def imagine_with_action(self, action, state, noise=None):
         """networks.py:145-152: open-loop rollout of given actions [B,T,A] from `state` {[B,...]}.
-        noise (tests): Exp(1) draws [T,B,S,D] for the prior samples; default = the Philox stream."""
+        noise (tests): Exp(1) draws [T,B,S,D] (continuous latents: N(0,1) draws [T,B,S]) for the prior samples;
+        default = the Philox stream."""
         assert isinstance(state, dict), state
         outs = []
         cur = state
@@ -336,6 +418,15 @@ class RSSM(nn.Module):
 
     def kl_loss(self, post, prior, free, dyn_scale, rep_scale):
         """networks.py:272-290 forward values: (loss, value, dyn_loss, rep_loss), each [B,T]."""
+        if not self._discrete:
+            t = (post["mean"], post["std"], prior["mean"], prior["std"])
+            if AG.wants_grad(*t):
+                return AG.GaussKLFn.apply(*t, free, dyn_scale, rep_scale)
+            t = [x.to(torch.float32).contiguous() for x in t]
+            kl = torch.empty(t[0].shape[:-1], device=t[0].device)
+            ops.gauss_kl_fwd(*t, kl)
+            clipped = torch.clip(kl, min=free)
+            return dyn_scale * clipped + rep_scale * clipped, kl, clipped, clipped.clone()
         if AG.wants_grad(post["logit"], prior["logit"]):
             return AG.KLLossFn.apply(post["logit"], prior["logit"], free, dyn_scale, rep_scale, self._unimix_ratio)
         pl, ql = post["logit"].contiguous(), prior["logit"].contiguous()

@@ -139,6 +139,39 @@ class IndependentOneHot:
         return self.base_dist.log_prob(x).sum(-1)
 
 
+class NormalLatent:
+    """What RSSM.get_dist returns for continuous latents (networks.py:167-171: ContDist(Independent(Normal(mean, std), 1)))
+    over the statistics `_suff_stats_layer` returned: mode() = mean, sample() = mean + std * eps (reparameterised),
+    entropy() summed over the last dim.  The actor's distribution is ContDist below."""
+
+    def __init__(self, mean, std, rng=None):
+        self.mean, self.stddev = mean, std
+        self._rng = rng
+
+    def mode(self):
+        return self.mean
+
+    def sample(self, sample_shape=(), noise=None):
+        if tuple(sample_shape) != ():
+            raise NotImplementedError("sample_shape")
+        rng = None
+        if noise is None:
+            rng = self._rng if self._rng is not None else default_rng(self.mean.device)
+        raw = torch.cat([self.mean, self.stddev], -1)
+        if AG.wants_grad(raw):
+            out = AG.GaussHeadFn.apply(raw, noise, rng, "none", "identity", 0.0, False)[2]
+        else:
+            out = torch.empty_like(self.mean, memory_format=torch.contiguous_format)
+            ops.gauss_head_fwd(raw.contiguous(), out, eps=None if noise is None else noise.to(torch.float32).contiguous(),
+                               rng=rng, mean_act="none", std_act="identity", min_std=0.0)
+        if rng is not None:
+            rng.commit()
+        return out
+
+    def entropy(self):
+        return AG.GaussEntropyFn.apply(self.mean, self.stddev)
+
+
 class DiscDist:
     """tools.py:463-517: 255-bucket symlog two-hot head."""
 

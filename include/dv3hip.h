@@ -171,6 +171,38 @@ int dv3_kl_bwd(const float* post_logit, const float* prior_logit, const float* k
                long rows, int S, int D, float unimix, float free_nats, float dyn_scale, float rep_scale,
                float upstream, int acc_post, int acc_prior, void* stream);
 
+/* ---- continuous Gaussian latents, dyn_discrete: 0 (csrc/gaussops.hip) -----------------------------
+ * dv3_gauss_head_fwd: raw [M, 2S] = mean_raw | std_raw (the stat layer's output, in torch.split's order) ->
+ *   mean = mean_act(mean_raw), std = std_act(std_raw) + min_std, stoch = mean + std * eps, each [M, S]
+ *   (RSSM._suff_stats_layer, networks.py:251-270, and the rsample of get_dist, networks.py:167-171).
+ *   mean_act: 0 none, 1 tanh5 (5 tanh(x/5)).  std_act: 0 softplus, 1 abs (|x+1|), 2 sigmoid, 3 sigmoid2 (2 sigmoid(x/2)),
+ *   4 identity (std_raw already is a standard deviation: sampling from the statistics _suff_stats_layer returned).
+ *   eps [M, S]: N(0,1) draws, or NULL for the Philox draws dv3_fill_normal would write into an [M, S] array at
+ *   rng_offset (bit-equal); eps_out (optional) receives the draws used.  mode = 1: stoch = mean, no draw.
+ *   mean / std may be NULL.  next_first [M], init [S], next_out [M, S] (all three or none): the next observe
+ *   step's reset blend of the sample, next_out = stoch (1 - next_first[m]) + init[s] next_first[m]
+ *   (networks.py:183-191), the counterpart of dv3_onehot_sample_fwd_blend.  S <= 1024.
+ * dv3_gauss_head_bwd: draw [M, 2S] (+)= { (dstoch + dmean) mean_act', (dstoch eps + dstd) std_act' }; dstoch, dmean,
+ *   dstd may each be NULL; mode = 1 (or the mean-only sample): no eps term.
+ * dv3_gauss_kl_fwd: kl[R] = sum_s KL(N(post_mean, post_std) || N(prior_mean, prior_std)) (the un-clipped `value` of
+ *   RSSM.kl_loss, networks.py:272-290), ent_*[R] = sum_s (1/2 + 1/2 ln 2 pi + ln std) (optional).
+ * dv3_gauss_kl_bwd: gradient of upstream * (dyn_scale max(KL(sg(post)||prior), free) + rep_scale max(KL(post||
+ *   sg(prior)), free)): the rep term reaches the posterior only, the dyn term the prior only; rows with kl >= free
+ *   pass, as in dv3_kl_bwd.  Each output may be NULL (not all four). */
+int dv3_gauss_head_fwd(const float* raw, const float* eps, const unsigned long long* rng_state,
+                       unsigned long long rng_offset, float* eps_out, float* mean, float* std_out, float* stoch,
+                       long M, int S, int mean_act, int std_act, float min_std, int mode, const float* next_first,
+                       const float* init, float* next_out, void* stream);
+int dv3_gauss_head_bwd(const float* dstoch, const float* dmean, const float* dstd, const float* raw,
+                       const float* eps, float* draw, long M, int S, int mean_act, int std_act, int mode,
+                       int accumulate, void* stream);
+int dv3_gauss_kl_fwd(const float* post_mean, const float* post_std, const float* prior_mean, const float* prior_std,
+                     float* kl, float* ent_post, float* ent_prior, long R, int S, void* stream);
+int dv3_gauss_kl_bwd(const float* post_mean, const float* post_std, const float* prior_mean, const float* prior_std,
+                     const float* kl, float* dpost_mean, float* dpost_std, float* dprior_mean, float* dprior_std,
+                     long R, int S, float free_nats, float dyn_scale, float rep_scale, float upstream, int acc_post,
+                     int acc_prior, void* stream);
+
 /* ---- 255-bucket symlog two-hot head -- tools.DiscDist (tools.py:463-517) --------------------------
  * logits [R,255].  mode: symexp(sum softmax*linspace(-20,20,255)).  logprob: two-hot cross-entropy of
  * symlog(x[r]).  bwd: dlogits (+)= up[r] * d(out[r])/dlogits. */
