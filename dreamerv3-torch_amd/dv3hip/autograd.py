@@ -350,63 +350,68 @@ def _rssm_shadow(params: Sequence[torch.Tensor]) -> E.PRSSM:
                    E.PLin(*s[13:15]), E.PLin(*s[15:17]))
 
 
+def _observe_forward(ctx, embed_tm, action_tm, first_tm, q_prior, q_post, rng, dims, params, keys):
+    """Forward of both observe nodes: a private engine over shadow parameters runs observe_fwd, ctx keeps it for the
+    backward, and the outputs are clones of the engine's buffers `keys`."""
+    P = _rssm_shadow(params)
+    eng = E.RSSMEngine(P, E.Workspace(embed_tm.device), **dims)
+    f32 = lambda x: x.detach().to(F32).contiguous()
+    out = eng.observe_fwd(f32(embed_tm), f32(action_tm), f32(first_tm), q_prior=q_prior, q_post=q_post, rng=rng)
+    ctx.eng, ctx.P, ctx.out = eng, P, out
+    ctx.set_materialize_grads(False)
+    return tuple(out[k].clone() for k in keys)
+
+
+def _observe_backward_tail(ctx, side, dembed):
+    """Behind observe_bwd (which returned `side`): the gradients of both observe nodes' 7 inputs + 17 parameters."""
+    side.join()
+    grads = [p.grad if ctx.needs_input_grad[7 + i] else None for i, p in enumerate(rssm_param_list(ctx.P))]
+    ctx.eng = ctx.out = None
+    return (dembed if ctx.needs_input_grad[0] else None, None, None, None, None, None, None) + tuple(grads)
+
+
 class ObserveFn(Function):
     """networks.RSSM.observe (networks.py:127-143) on time-major inputs.  Outputs (post_stoch, post_logit, deter,
     prior_stoch, prior_logit), each [T,B,...]; gradients flow to `embed` and the 17 RSSM parameters (the action
     and the reset flags are data)."""
 
+    KEYS = ("post_stoch", "post_logit", "deter", "prior_stoch", "prior_logit")  # observe_fwd's names of the outputs
+
     @staticmethod
     def forward(ctx, embed_tm, action_tm, first_tm, q_prior, q_post, rng, dims, *params):
-        P = _rssm_shadow(params)
-        eng = E.RSSMEngine(P, E.Workspace(embed_tm.device), **dims)
-        emb = embed_tm.detach().to(F32).contiguous()
-        out = eng.observe_fwd(emb, action_tm.detach().to(F32).contiguous(), first_tm.detach().to(F32).contiguous(),
-                              q_prior=q_prior, q_post=q_post, rng=rng)
-        ctx.eng, ctx.P, ctx.out = eng, P, out
-        ctx.set_materialize_grads(False)
-        return (out["post_stoch"].clone(), out["post_logit"].clone(), out["deter"].clone(), out["prior_stoch"].clone(),
-                out["prior_logit"].clone())
+        return _observe_forward(ctx, embed_tm, action_tm, first_tm, q_prior, q_post, rng, dims, params, ObserveFn.KEYS)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, d_ps, d_pl, d_dt, d_qs, d_ql):
-        eng, P, out = ctx.eng, ctx.P, ctx.out
+        eng, out = ctx.eng, ctx.out
         T, B, S, D, De = eng.T, eng.B, eng.S, eng.D, eng.De
-        dev = out["deter"].device
-        dpl = _c(d_pl, shape=(T, B, S, D), like=out["deter"])
-        dql = _c(d_ql, shape=(T, B, S, D), like=out["deter"])
+        like = out["deter"]
+        dpl = _c(d_pl, shape=(T, B, S, D), like=like)
+        dql = _c(d_ql, shape=(T, B, S, D), like=like)
         if d_qs is not None:  # the prior sample's straight-through path into its logits
             ops.onehot_st_bwd(out["prior_logit"], _c(d_qs.reshape(T, B, S, D)), dql, unimix=eng.unimix, accumulate=True)
-        gs = _c(None if d_ps is None else d_ps.reshape(T, B, S * D), shape=(T, B, S * D), like=out["deter"])
-        gd = _c(d_dt, shape=(T, B, De), like=out["deter"])
-        dembed = torch.empty(T, B, eng.E, device=dev, dtype=F32)
-        side = eng.observe_bwd(dpl, dql, gs, gd, dembed)
-        side.join()
-        grads = [p.grad if ctx.needs_input_grad[7 + i] else None for i, p in enumerate(rssm_param_list(P))]
-        ctx.eng = ctx.out = None
-        return (dembed if ctx.needs_input_grad[0] else None, None, None, None, None, None, None) + tuple(grads)
+        gs = _c(None if d_ps is None else d_ps.reshape(T, B, S * D), shape=(T, B, S * D), like=like)
+        gd = _c(d_dt, shape=(T, B, De), like=like)
+        dembed = torch.empty(T, B, eng.E, device=like.device, dtype=F32)
+        return _observe_backward_tail(ctx, eng.observe_bwd(dpl, dql, gs, gd, dembed), dembed)
 
 
 class ObserveGaussFn(Function):
     """ObserveFn for continuous latents.  Outputs (post_stoch, post_mean, post_std, deter, prior_stoch, prior_mean,
     prior_std), each [T,B,...]; eps_prior / eps_post [T,B,S] ~ N(0,1) or the rng stream."""
 
+    KEYS = ("post_stoch", "post_mean", "post_std", "deter", "prior_stoch", "prior_mean", "prior_std")
+
     @staticmethod
     def forward(ctx, embed_tm, action_tm, first_tm, eps_prior, eps_post, rng, dims, *params):
-        P = _rssm_shadow(params)
-        eng = E.RSSMEngine(P, E.Workspace(embed_tm.device), **dims)
-        emb = embed_tm.detach().to(F32).contiguous()
-        out = eng.observe_fwd(emb, action_tm.detach().to(F32).contiguous(), first_tm.detach().to(F32).contiguous(),
-                              q_prior=eps_prior, q_post=eps_post, rng=rng)
-        ctx.eng, ctx.P, ctx.out = eng, P, out
-        ctx.set_materialize_grads(False)
-        return tuple(out[k].clone() for k in ("post_stoch", "post_mean", "post_std", "deter", "prior_stoch",
-                                              "prior_mean", "prior_std"))
+        return _observe_forward(ctx, embed_tm, action_tm, first_tm, eps_prior, eps_post, rng, dims, params,
+                                ObserveGaussFn.KEYS)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, d_ps, d_pm, d_psd, d_dt, d_qs, d_qm, d_qsd):
-        eng, P, out = ctx.eng, ctx.P, ctx.out
+        eng, out = ctx.eng, ctx.out
         T, B, S, De = eng.T, eng.B, eng.S, eng.De
         like = out["deter"]
         cc = lambda t: None if t is None else _c(t.reshape(T, B, S))
@@ -414,10 +419,7 @@ class ObserveGaussFn(Function):
         gd = _c(d_dt, shape=(T, B, De), like=like)
         dembed = torch.empty(T, B, eng.E, device=like.device, dtype=F32)
         side = eng.observe_bwd((cc(d_pm), cc(d_psd)), (cc(d_qm), cc(d_qsd), cc(d_qs)), gs, gd, dembed)
-        side.join()
-        grads = [p.grad if ctx.needs_input_grad[7 + i] else None for i, p in enumerate(rssm_param_list(P))]
-        ctx.eng = ctx.out = None
-        return (dembed if ctx.needs_input_grad[0] else None, None, None, None, None, None, None) + tuple(grads)
+        return _observe_backward_tail(ctx, side, dembed)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -630,6 +630,15 @@ class MLPEngine:
 # ---------------------------------------------------------------------------------------------
 # RSSM scans
 # ---------------------------------------------------------------------------------------------
+def _scan_bandwidth_bound(De: int, Hd: int, B: int) -> bool:
+    """Whether the observe scans are bandwidth-bound with B rows per step: once a step streams more GRU weights than
+    half of the chip's L2 / Infinity-Cache paths deliver in its fixed launch cost (or has more rows than the few-row
+    GEMMs take), the chain wants every compute unit and sharing the chip does not pay (RSSMEngine.lanes_pay,
+    RSSMEngine.pipeline_mode)."""
+    gru_weight_bytes = 4 * 3 * De * (Hd + De)
+    return gru_weight_bytes > (32 << 20) or B > 64
+
+
 class RSSMEngine:
     def __init__(self, P: PRSSM, ws: Workspace, *, stoch: int, discrete: int, deter: int, hidden: int,
                  num_actions: int, embed: int, unimix: float, mean_act: str = "none", std_act: str = "softplus",
@@ -643,10 +652,9 @@ class RSSMEngine:
         self.SD = stoch if self.gauss else stoch * discrete  # width of the flattened stochastic state
         self.SW = 2 * stoch if self.gauss else self.SD  # width of the stat layers' output
         self.unimix = unimix
+        # keyword arguments of ops.gauss_head_fwd / ops.gauss_head_bwd (the backward does not need min_std)
         self.head = dict(mean_act=mean_act, std_act=std_act, min_std=float(min_std))
-
-    def _head_bwd_kw(self):
-        return dict(mean_act=self.head["mean_act"], std_act=self.head["std_act"])
+        self.head_bwd = dict(mean_act=mean_act, std_act=std_act)
 
     # -- initial state (networks.py:99-123, 235-239): deter0 = tanh(W), stoch0 = mode(prior head) -----
     def init_state_fwd(self):
@@ -675,7 +683,7 @@ class RSSMEngine:
         m0, r0 = ws.get("init.m", (1,)), ws.get("init.r", (1,))
         dl0 = ws.get("init.dlogit", (1, self.SW))
         if self.gauss:
-            ops.gauss_head_bwd(l0, dl0, dstoch=dstoch0.view(1, self.S), mode=True, **self._head_bwd_kw())
+            ops.gauss_head_bwd(l0, dl0, dstoch=dstoch0.view(1, self.S), mode=True, **self.head_bwd)
         else:
             ops.onehot_st_bwd(l0.view(self.S, self.D), dstoch0.view(self.S, self.D), dl0.view(self.S, self.D),
                               unimix=self.unimix, mode=True)
@@ -691,45 +699,75 @@ class RSSMEngine:
         ops.tanh_bwd(d0, dd, _g(P.W0), accumulate=True)
 
     # -- observe ------------------------------------------------------------------------------------
+    def _scan_acts(self):
+        """The forward activations of the observe scan that do not depend on the latent kind, time-major [T,B,...]:
+        observe_fwd writes them, observe_bwd reads them.  In order: first, sin, din, ain (the reset flags and the blended
+        step inputs), x1pre/x1/m1/r1 (img_in), gpre/mg/rg (GRU), deter, x3pre/x3/m3/r3 (obs_out), x2pre/x2/m2/r2
+        (img_out, batched)."""
+        T, B, SD, De, Hd, A = self.T, self.B, self.SD, self.De, self.Hd, self.A
+        g = self.ws.get
+        return (g("obs.first", (T, B)), g("obs.sin", (T, B, SD)), g("obs.din", (T, B, De)), g("obs.ain", (T, B, A)),
+                g("obs.x1pre", (T, B, Hd)), g("obs.x1", (T, B, Hd)), g("obs.m1", (T, B)), g("obs.r1", (T, B)),
+                g("obs.gpre", (T, B, 3 * De)), g("obs.mg", (T, B)), g("obs.rg", (T, B)),
+                g("obs.deter", (T, B, De)),
+                g("obs.x3pre", (T, B, Hd)), g("obs.x3", (T, B, Hd)), g("obs.m3", (T, B)), g("obs.r3", (T, B)),
+                g("obs.x2pre", (T, B, Hd)), g("obs.x2", (T, B, Hd)), g("obs.m2", (T, B)), g("obs.r2", (T, B)))
+
     def observe_fwd(self, embed_tm, action_tm, first_tm, *, q_prior=None, q_post=None, rng=None, force=None,
                     state0=None):
         """embed_tm [T,B,E], action_tm [T,B,A], first_tm [T,B] (float 0/1; row 0 is forced to 1, as
-        prev_state=None does in networks.py:176-180).  Noise [T,B,S,D] ~ Exp(1) or rng state.
-        force (parity tests): dict(post=[T,B,S] int32, prior=[T,B,S] int32, flips=int32[1]) teacher-forces the
-        sampled classes and counts the draws that differ.  state0 = (stoch [B,SD], deter [B,De]): the carried
-        state of RSSM.observe(..., state) (networks.py:127-143): step 0 then blends it with is_first[:, 0] as given
-        instead of starting every row from the initial state.  Returns dict of time-major buffers."""
+        prev_state=None does in networks.py:176-180).  Step by step
+            [blend (t = 0 or wide cells)] -> img_in -> GRU GEMM -> gates (+ next deter blend)
+            -> obs_out GEMM (deter half) -> LN/SiLU + stat GEMM (one launch where ops.scan_ln_gemm_ok(Hd, SW))
+            -> posterior sample (+ next stoch blend)
+        then the prior head for all steps at once.  The two latent kinds differ in the sampler and in what rides on it:
+
+        categorical: q_prior / q_post [T,B,S,D] ~ Exp(1) or the rng stream; img_in gathers weight columns by the class
+        indices of the one-hot input, and the sample of step t may run in one launch with img_in of step t+1.
+        force (parity tests): dict(post=[T,B,S] int32, prior=[T,B,S] int32, flips=int32[1]) teacher-forces the sampled
+        classes and counts the draws that differ.  Returns post_stoch / post_logit / prior_stoch / prior_logit
+        [T,B,S,D], deter, action, post_idx [T,B,S] int32.
+
+        Gaussian: q_prior / q_post [T,B,S] ~ N(0,1) or the rng stream; every layer is dense, the sampler is
+        ops.gauss_head_fwd on the stat layer's [T,B,2S] output (mean_raw | std_raw).  force raises: a Gaussian draw is
+        injected as noise.  The prior's sample is drawn although nothing consumes it, as the reference does
+        (networks.py:195, 228-229).  Returns post_stoch / post_mean / post_std [T,B,S], post_raw [T,B,2S], the same
+        four of the prior, deter, action.
+
+        state0 = (stoch [B,SD], deter [B,De]): the carried state of RSSM.observe(..., state) (networks.py:127-143):
+        step 0 then blends it with is_first[:, 0] as given instead of starting every row from the initial state.
+        Returns a dict of time-major buffers."""
         P, ws = self.P, self.ws
         T, B = embed_tm.shape[0], embed_tm.shape[1]
-        S, D, SD, De, Hd, A, E = self.S, self.D, self.SD, self.De, self.Hd, self.A, self.E
+        S, D, SD, SW, De, Hd, A, E = self.S, self.D, self.SD, self.SW, self.De, self.Hd, self.A, self.E
+        gauss = self.gauss
         self.T, self.B = T, B
         TB = T * B
-        if self.gauss:
-            if force:
-                raise ValueError("teacher forcing is for the categorical draws: a Gaussian draw is injected as noise")
-            return self._observe_fwd_gauss(embed_tm, action_tm, first_tm, eps_prior=q_prior, eps_post=q_post, rng=rng,
-                                           state0=state0)
+        if gauss and force:
+            raise ValueError("teacher forcing is for the categorical draws: a Gaussian draw is injected as noise")
         force = force or {}
         f_post, f_prior, flips = force.get("post"), force.get("prior"), force.get("flips")
         s0, d0 = self.init_state_fwd()
-        first = ws.get("obs.first", (T, B))
+        first, sin, din, ain, x1pre, x1, m1, r1, gpre, mg, rg, deter, x3pre, x3, m3, r3, x2pre, x2, m2, r2 = \
+            self._scan_acts()
         first.copy_(first_tm)
         if state0 is None:
             first[0].fill_(1.0)
         g = ws.get
-        sin, din, ain = g("obs.sin", (T, B, SD)), g("obs.din", (T, B, De)), g("obs.ain", (T, B, A))
-        x1pre, x1 = g("obs.x1pre", (T, B, Hd)), g("obs.x1", (T, B, Hd))
-        m1, r1 = g("obs.m1", (T, B)), g("obs.r1", (T, B))
-        gpre, mg, rg = g("obs.gpre", (T, B, 3 * De)), g("obs.mg", (T, B)), g("obs.rg", (T, B))
-        deter = g("obs.deter", (T, B, De))
-        x3pre, x3 = g("obs.x3pre", (T, B, Hd)), g("obs.x3", (T, B, Hd))
-        m3, r3 = g("obs.m3", (T, B)), g("obs.r3", (T, B))
-        post_logit, post_stoch = g("obs.post_logit", (T, B, S, D)), g("obs.post_stoch", (T, B, S, D))
-        # class indices of the (one-hot) posterior samples and of the blended step inputs: the Linears that read
-        # them gather weight columns instead of multiplying the one-hot (ops.onehot_linear_ln)
-        post_idx, idx_in = g("obs.post_idx", (T, B, S), torch.int32), g("obs.idx_in", (T, B, S), torch.int32)
-        init_idx = g("init.idx", (S,), torch.int32)
-        gather = _GATHER_OBS
+        lat = (S,) if gauss else (S, D)  # one latent
+        post_stoch, prior_stoch = g("obs.post_stoch", (T, B) + lat), g("obs.prior_stoch", (T, B) + lat)
+        if gauss:
+            post_stat, prior_stat = g("obs.post_raw", (T, B, SW)), g("obs.prior_raw", (T, B, SW))
+            post_eps, prior_eps = g("obs.post_eps", (T, B, S)), g("obs.prior_eps", (T, B, S))
+            post_mean, post_std = g("obs.post_mean", (T, B, S)), g("obs.post_std", (T, B, S))
+            prior_mean, prior_std = g("obs.prior_mean", (T, B, S)), g("obs.prior_std", (T, B, S))
+        else:
+            post_stat, prior_stat = g("obs.post_logit", (T, B, S, D)), g("obs.prior_logit", (T, B, S, D))
+            # class indices of the (one-hot) posterior samples and of the blended step inputs: the Linears that read
+            # them gather weight columns instead of multiplying the one-hot (ops.onehot_linear_ln)
+            post_idx, idx_in = g("obs.post_idx", (T, B, S), torch.int32), g("obs.idx_in", (T, B, S), torch.int32)
+            init_idx = g("init.idx", (S,), torch.int32)
+        gather = _GATHER_OBS and not gauss
         if gather:
             # (a copy of its own: the imagination of the PREVIOUS update may be reading "rssm.img_in_wt" while this
             # scan runs beside it -- graph.UpdateRunner.step_pipelined)
@@ -742,7 +780,7 @@ class RSSMEngine:
         ops.reset_blend(v2(action_tm, A), None, first.view(TB), v2(ain, A))
         fuse = ((De % 256 == 0 and De <= 1024) or (De % 1024 == 0 and De <= 4096)) and _FUSE_BLEND
         fuse_in = fuse and gather and _FUSE_SAMPLE_IN and ops.sample_linear_ln_ok(S, D, Hd) and Hd % 4 == 0
-        fuse_row = _FUSE_SCAN_ROW and _FUSE_SCAN_LN and B <= 64 and ops.scan_ln_gemm_ok(Hd, SD)
+        fuse_row = _FUSE_SCAN_ROW and _FUSE_SCAN_LN and B <= 64 and ops.scan_ln_gemm_ok(Hd, SW)
         Cuts.mark("wm.fscan")  # (pipelined capture: the forward scan is a lane segment of its own)
         for t in range(T):
             if T >= 16 and t == (3 * T) // 4:
@@ -765,15 +803,19 @@ class RSSMEngine:
             ops.gru_fwd(gpre[t], P.gru.g, P.gru.b, din[t], deter[t], mg[t], rg[t],
                         next_blend=(first[t + 1], d0.view(De), din[t + 1]) if nxt else None)
             ops.gemm(deter[t], P.obs_out.W[:, :De], x3pre[t], accumulate=True)
-            if fuse_row:  # the obs_out LayerNorm rides in the logit GEMM (5 launches per step instead of 6)
+            if fuse_row:  # the obs_out LayerNorm rides in the stat GEMM (5 launches per step instead of 6)
                 ops.scan_ln_gemm(x3pre[t], P.obs_out.g, P.obs_out.b, x3[t], m3[t], r3[t], P.obs.W,
-                                 post_logit[t].view(B, SD), bias=P.obs.b)
+                                 post_stat[t].view(B, SW), bias=P.obs.b)
             else:
                 ops.ln_act_fwd(x3pre[t], P.obs_out.g, P.obs_out.b, x3[t], m3[t], r3[t], act=True)
-                ops.gemm(x3[t], P.obs.W, post_logit[t].view(B, SD), bias=P.obs.b)
-            if fuse_in and nxt:
+                ops.gemm(x3[t], P.obs.W, post_stat[t].view(B, SW), bias=P.obs.b)
+            if gauss:
+                ops.gauss_head_fwd(post_stat[t], post_stoch[t], post_mean[t], post_std[t],
+                                   eps=None if q_post is None else q_post[t], rng=rng, eps_out=post_eps[t],
+                                   next_blend=(first[t + 1], s0.view(S), sin[t + 1]) if nxt else None, **self.head)
+            elif fuse_in and nxt:
                 # the posterior sample of this step and the img_in layer of the next one in one launch
-                ops.onehot_sample_linear_ln(post_logit[t], post_stoch[t], noise=None if q_post is None else q_post[t],
+                ops.onehot_sample_linear_ln(post_stat[t], post_stoch[t], noise=None if q_post is None else q_post[t],
                                             rng=rng, unimix=self.unimix, idx=post_idx[t].view(-1),
                                             forced=None if f_post is None else f_post[t], flips=flips,
                                             next_first=first[t + 1], init=s0.view(SD), init_idx=init_idx,
@@ -781,103 +823,34 @@ class RSSMEngine:
                                             WT=wt_in, x2=ain[t + 1], pre=x1pre[t + 1], gamma=P.img_in.g,
                                             beta=P.img_in.b, y=x1[t + 1], mean=m1[t + 1], rstd=r1[t + 1])
             else:
-                ops.onehot_sample(post_logit[t], post_stoch[t], noise=None if q_post is None else q_post[t], rng=rng,
+                ops.onehot_sample(post_stat[t], post_stoch[t], noise=None if q_post is None else q_post[t], rng=rng,
                                   unimix=self.unimix,
                                   next_blend=(first[t + 1], s0.view(SD), sin[t + 1].view(B, S, D), init_idx,
                                               idx_in[t + 1].view(-1)) if nxt else None,
                                   forced=None if f_post is None else f_post[t], flips=flips, idx=post_idx[t].view(-1))
         Cuts.mark("wm.mid")
         # prior head for all steps at once
-        x2pre, x2 = g("obs.x2pre", (T, B, Hd)), g("obs.x2", (T, B, Hd))
-        m2, r2 = g("obs.m2", (T, B)), g("obs.r2", (T, B))
-        prior_logit, prior_stoch = g("obs.prior_logit", (T, B, S, D)), g("obs.prior_stoch", (T, B, S, D))
         dense_ln_fwd(P.img_out, v2(deter, De), None, v2(x2pre, Hd), m2.view(TB), r2.view(TB), v2(x2, Hd))
-        ops.gemm(v2(x2, Hd), P.ims.W, v2(prior_logit, SD), bias=P.ims.b)
-        ops.onehot_sample(prior_logit, prior_stoch, noise=q_prior, rng=rng, unimix=self.unimix, forced=f_prior,
+        ops.gemm(v2(x2, Hd), P.ims.W, v2(prior_stat, SW), bias=P.ims.b)
+        self._embed = embed_tm
+        if gauss:
+            ops.gauss_head_fwd(prior_stat, prior_stoch, prior_mean, prior_std, eps=q_prior, rng=rng, eps_out=prior_eps,
+                               **self.head)
+            return dict(post_stoch=post_stoch, post_mean=post_mean, post_std=post_std, post_raw=post_stat, deter=deter,
+                        prior_stoch=prior_stoch, prior_mean=prior_mean, prior_std=prior_std, prior_raw=prior_stat,
+                        action=ain)
+        ops.onehot_sample(prior_stat, prior_stoch, noise=q_prior, rng=rng, unimix=self.unimix, forced=f_prior,
                           flips=flips)
-        self._embed = embed_tm
-        return dict(post_stoch=post_stoch, post_logit=post_logit, deter=deter, prior_stoch=prior_stoch,
-                    prior_logit=prior_logit, action=ain, post_idx=post_idx)
-
-    def _observe_fwd_gauss(self, embed_tm, action_tm, first_tm, *, eps_prior, eps_post, rng, state0):
-        """observe_fwd for continuous latents: the dense (no gather) branches of the scan above, step by step
-            [blend (t = 0 or wide cells)] -> img_in GEMM -> LN/SiLU -> GRU GEMM -> gates (+ next deter blend)
-            -> obs_out GEMM (deter half) -> LN/SiLU + stat GEMM (one launch where ops.scan_ln_gemm_ok(Hd, 2S))
-            -> gauss_head_fwd (+ next stoch blend)
-        eps_prior / eps_post [T,B,S] ~ N(0,1) or the rng stream.  The prior's sample is drawn although nothing
-        consumes it, as the reference does (networks.py:195, 228-229)."""
-        P, ws = self.P, self.ws
-        T, B = embed_tm.shape[0], embed_tm.shape[1]
-        S, De, Hd, A, E = self.S, self.De, self.Hd, self.A, self.E
-        self.T, self.B = T, B
-        TB = T * B
-        s0, d0 = self.init_state_fwd()
-        first = ws.get("obs.first", (T, B))
-        first.copy_(first_tm)
-        if state0 is None:
-            first[0].fill_(1.0)
-        g = ws.get
-        sin, din, ain = g("obs.sin", (T, B, S)), g("obs.din", (T, B, De)), g("obs.ain", (T, B, A))
-        x1pre, x1 = g("obs.x1pre", (T, B, Hd)), g("obs.x1", (T, B, Hd))
-        m1, r1 = g("obs.m1", (T, B)), g("obs.r1", (T, B))
-        gpre, mg, rg = g("obs.gpre", (T, B, 3 * De)), g("obs.mg", (T, B)), g("obs.rg", (T, B))
-        deter = g("obs.deter", (T, B, De))
-        x3pre, x3 = g("obs.x3pre", (T, B, Hd)), g("obs.x3", (T, B, Hd))
-        m3, r3 = g("obs.m3", (T, B)), g("obs.r3", (T, B))
-        post_raw, post_eps = g("obs.post_raw", (T, B, 2 * S)), g("obs.post_eps", (T, B, S))
-        post_mean, post_std, post_stoch = g("obs.post_mean", (T, B, S)), g("obs.post_std", (T, B, S)), \
-            g("obs.post_stoch", (T, B, S))
-        ops.gemm(v2(embed_tm, E), P.obs_out.W[:, De:], v2(x3pre, Hd))
-        ops.reset_blend(v2(action_tm, A), None, first.view(TB), v2(ain, A))
-        fuse = ((De % 256 == 0 and De <= 1024) or (De % 1024 == 0 and De <= 4096)) and _FUSE_BLEND
-        fuse_row = _FUSE_SCAN_ROW and _FUSE_SCAN_LN and B <= 64 and ops.scan_ln_gemm_ok(Hd, 2 * S)
-        Cuts.mark("wm.fscan")
-        for t in range(T):
-            if T >= 16 and t == (3 * T) // 4:
-                Cuts.mark("wm.fscan2")
-            if t == 0 or not fuse:
-                prev_s = post_stoch[t - 1] if t > 0 else (None if state0 is None else state0[0])
-                prev_d = deter[t - 1] if t > 0 else (None if state0 is None else state0[1])
-                ops.obs_blend(prev_s, s0.view(S), prev_d, d0.view(De), action_tm[t], first[t], sin[t], din[t], ain[t])
-            nxt = fuse and t + 1 < T
-            dense_ln_fwd(P.img_in, sin[t], ain[t], x1pre[t], m1[t], r1[t], x1[t])
-            ops.gemm(x1[t], P.gru.W, gpre[t], A2=din[t])
-            ops.gru_fwd(gpre[t], P.gru.g, P.gru.b, din[t], deter[t], mg[t], rg[t],
-                        next_blend=(first[t + 1], d0.view(De), din[t + 1]) if nxt else None)
-            ops.gemm(deter[t], P.obs_out.W[:, :De], x3pre[t], accumulate=True)
-            if fuse_row:
-                ops.scan_ln_gemm(x3pre[t], P.obs_out.g, P.obs_out.b, x3[t], m3[t], r3[t], P.obs.W, post_raw[t],
-                                 bias=P.obs.b)
-            else:
-                ops.ln_act_fwd(x3pre[t], P.obs_out.g, P.obs_out.b, x3[t], m3[t], r3[t], act=True)
-                ops.gemm(x3[t], P.obs.W, post_raw[t], bias=P.obs.b)
-            ops.gauss_head_fwd(post_raw[t], post_stoch[t], post_mean[t], post_std[t],
-                               eps=None if eps_post is None else eps_post[t], rng=rng, eps_out=post_eps[t],
-                               next_blend=(first[t + 1], s0.view(S), sin[t + 1]) if nxt else None, **self.head)
-        Cuts.mark("wm.mid")
-        # prior head for all steps at once
-        x2pre, x2 = g("obs.x2pre", (T, B, Hd)), g("obs.x2", (T, B, Hd))
-        m2, r2 = g("obs.m2", (T, B)), g("obs.r2", (T, B))
-        prior_raw, prior_eps = g("obs.prior_raw", (T, B, 2 * S)), g("obs.prior_eps", (T, B, S))
-        prior_mean, prior_std, prior_stoch = g("obs.prior_mean", (T, B, S)), g("obs.prior_std", (T, B, S)), \
-            g("obs.prior_stoch", (T, B, S))
-        dense_ln_fwd(P.img_out, v2(deter, De), None, v2(x2pre, Hd), m2.view(TB), r2.view(TB), v2(x2, Hd))
-        ops.gemm(v2(x2, Hd), P.ims.W, v2(prior_raw, 2 * S), bias=P.ims.b)
-        ops.gauss_head_fwd(prior_raw, prior_stoch, prior_mean, prior_std, eps=eps_prior, rng=rng, eps_out=prior_eps,
-                           **self.head)
-        self._embed = embed_tm
-        return dict(post_stoch=post_stoch, post_mean=post_mean, post_std=post_std, post_raw=post_raw, deter=deter,
-                    prior_stoch=prior_stoch, prior_mean=prior_mean, prior_std=prior_std, prior_raw=prior_raw, action=ain)
+        return dict(post_stoch=post_stoch, post_logit=post_stat, deter=deter, prior_stoch=prior_stoch,
+                    prior_logit=prior_stat, action=ain, post_idx=post_idx)
 
     def lanes_pay(self, heavy_side: bool) -> bool:
         """Whether the reverse scan should run beside the deferred weight gradients on the two CU-masked lanes.
         Measured on MI355X (ms per update, lanes / in line): cfg 2 16.22 / 16.65, cfg 3 26.50 / 27.24 -- but cfg 1 (vector
         decoder: ~0.2 ms of deferred work against two host waits and three more graph launches) 12.95 / 12.79, cfg 5
-        (deter 2048: 100 MB of weights per scan step) 267.9 / 255.6, cfg 4 (deter 4096) 391.6 / 383.9: once a step of the
-        scan streams more weights than half of the chip's L2 / Infinity-Cache paths deliver in its fixed launch cost,
-        the chain is bandwidth-bound and wants every CU.  heavy_side: the deferred launches include the conv decoder's."""
-        gru_weight_bytes = 4 * 3 * self.De * (self.Hd + self.De)
-        return bool(heavy_side) and gru_weight_bytes <= (32 << 20) and self.B <= 64
+        (deter 2048: 100 MB of weights per scan step) 267.9 / 255.6, cfg 4 (deter 4096) 391.6 / 383.9: the bandwidth-bound
+        scan (_scan_bandwidth_bound) wants every CU.  heavy_side: the deferred launches include the conv decoder's."""
+        return bool(heavy_side) and not _scan_bandwidth_bound(self.De, self.Hd, self.B)
 
     def pipeline_mode(self, conv: bool):
         """How graph.UpdateRunner.step_pipelined runs the behaviour phase of update k beside the world-model phase of
@@ -888,49 +861,41 @@ class RSSMEngine:
         compute units as on 256, so two half-chip streams of independent work beat one whole-chip stream; cfg 1 (MLP
         encoder / decoder: the world-model phase is 7 ms of the 12.8, the behaviour lane would be the long pole)
         12.8 / 11.4 / 12.7.  conv: the world model has the convolutional encoder / decoder."""
-        gru_weight_bytes = 4 * 3 * self.De * (self.Hd + self.De)
-        if gru_weight_bytes > (32 << 20) or getattr(self, "B", 0) > 64:
-            return None  # (wide cells: the scans are bandwidth-bound and want every compute unit, see lanes_pay)
+        if _scan_bandwidth_bound(self.De, self.Hd, getattr(self, "B", 0)):  # (may be asked before any scan has set B)
+            return None  # (wide cells: the scans want every compute unit, see lanes_pay)
         return "lanes" if conv else "staged"
 
     def observe_bwd(self, dpost_logit, dprior_logit, gs, gd, dembed, extra_side=None, lanes_pay=False):
         """Backward of observe_fwd.
 
-        dpost_logit/dprior_logit [T,B,S,D]: gradient on the logits (from the KL; dpost_logit is updated in
-        place with the straight-through term).  gs [T,B,SD], gd [T,B,De]: gradient on post stoch / deter
-        from the heads (both are used as scratch).  dembed [T,B,E] receives the encoder-output gradient.
-        All RSSM parameter gradients are accumulated into their .grad views.  extra_side: callables (weight
-        gradients of the heads / decoder) to run on the side stream beside the reverse scan; lanes_pay: what
-        self.lanes_pay() said about them.  Returns the SideStream so that the caller can put more work beside the encoder
-        backward and join()."""
+        The gradient on the two heads' statistics (from the KL) comes in dpost_logit / dprior_logit:
+        categorical: each [T,B,S,D], on the logits; dpost_logit is updated in place with the straight-through term (the
+        prior sample's own straight-through term, if any, is the caller's to add into dprior_logit).
+        Gaussian: dpost_logit = (dmean, dstd), each [T,B,S] or None, on the posterior's mean / std; dprior_logit =
+        (dmean, dstd, dstoch), each [T,B,S] or None, on the prior's mean / std / sample.  Both are folded through the
+        head's activations here (ops.gauss_head_bwd), the prior's for all steps at once.
+        gs [T,B,SD], gd [T,B,De]: gradient on post stoch / deter from the heads (both are used as scratch).
+        dembed [T,B,E] receives the encoder-output gradient.  All RSSM parameter gradients are accumulated into their
+        .grad views.  extra_side: callables (weight gradients of the heads / decoder) to run on the side stream beside
+        the reverse scan; lanes_pay: what self.lanes_pay() said about them.  Returns the SideStream so that the caller
+        can put more work beside the encoder backward and join()."""
         P, ws = self.P, self.ws
         T, B, S, D, SD, De, Hd, A, E = self.T, self.B, self.S, self.D, self.SD, self.De, self.Hd, self.A, self.E
         TB = T * B
         g = ws.get
-        first = g("obs.first", (T, B))
-        sin, din, ain = g("obs.sin", (T, B, SD)), g("obs.din", (T, B, De)), g("obs.ain", (T, B, A))
-        x1pre, x1 = g("obs.x1pre", (T, B, Hd)), g("obs.x1", (T, B, Hd))
-        m1, r1 = g("obs.m1", (T, B)), g("obs.r1", (T, B))
-        gpre, mg, rg = g("obs.gpre", (T, B, 3 * De)), g("obs.mg", (T, B)), g("obs.rg", (T, B))
-        deter = g("obs.deter", (T, B, De))
-        x3pre, x3 = g("obs.x3pre", (T, B, Hd)), g("obs.x3", (T, B, Hd))
-        m3, r3 = g("obs.m3", (T, B)), g("obs.r3", (T, B))
+        first, sin, din, ain, x1pre, x1, m1, r1, gpre, mg, rg, deter, x3pre, x3, m3, r3, x2pre, x2, m2, r2 = \
+            self._scan_acts()
         gauss, SW = self.gauss, self.SW
         if gauss:
-            # dpost_logit = (dmean, dstd) [T,B,S] on the posterior's statistics (from the KL; either may be None);
-            # dprior_logit = (dmean, dstd, dstoch) on the prior's: folded through the prior head's activations here,
-            # for all steps at once
             dpost_mean, dpost_std = dpost_logit
             post_raw, post_eps = g("obs.post_raw", (T, B, SW)), g("obs.post_eps", (T, B, S))
             dprior_logit_g = g("obs.dprior_raw", (T, B, SW))
             ops.gauss_head_bwd(g("obs.prior_raw", (T, B, SW)), dprior_logit_g, dmean=dprior_logit[0],
                                dstd=dprior_logit[1], dstoch=dprior_logit[2], eps=g("obs.prior_eps", (T, B, S)),
-                               **self._head_bwd_kw())
+                               **self.head_bwd)
             dprior_logit = dprior_logit_g
         else:
             post_logit = g("obs.post_logit", (T, B, S, D))
-        x2pre, x2 = g("obs.x2pre", (T, B, Hd)), g("obs.x2", (T, B, Hd))
-        m2, r2 = g("obs.m2", (T, B)), g("obs.r2", (T, B))
         # ---- prior head, batched: prior_logit -> ims -> LN/SiLU -> img_out -> deter
         dx2 = g("obs.dx2", (TB, Hd))
         dpl2 = v2(dprior_logit, SW)
@@ -1005,7 +970,7 @@ class RSSMEngine:
                     ops.gauss_head_bwd(post_raw[t], dpl_out[t], dstoch=gs_t,
                                        dmean=None if dpost_mean is None else dpost_mean[t],
                                        dstd=None if dpost_std is None else dpost_std[t], eps=post_eps[t],
-                                       **self._head_bwd_kw())
+                                       **self.head_bwd)
                     ops.gemm(dpl_out[t], P.obs.W, dx3[t], transB=False, accumulate="atomic")
                 else:
                     if t == T - 1 or not fuse_carry:  # (otherwise done by step t+1's fused carry + straight-through launch)
@@ -1141,7 +1106,7 @@ class RSSMEngine:
         S, D, SD, De, Hd = self.S, self.D, self.SD, self.De, self.Hd
         dlogit = scratch["dlogit"]  # [M, SW]
         if self.gauss:
-            ops.gauss_head_bwd(bufs["raw"], dlogit, dstoch=dstoch, eps=bufs["eps"], **self._head_bwd_kw())
+            ops.gauss_head_bwd(bufs["raw"], dlogit, dstoch=dstoch, eps=bufs["eps"], **self.head_bwd)
         else:
             ops.onehot_st_bwd(bufs["logit"], dstoch.view(M, S, D), dlogit.view(M, S, D), unimix=self.unimix)
         if wt is not None:  # transposed weights (pack_bwd): every data gradient in the y = x B^T form

@@ -401,11 +401,7 @@ class WorldModel(nn.Module):
                        rep_scale=cfg.rep_scale, dyn_loss=acc[4], rep_loss=acc[4], kl=ws.get("wm.kl_mean", (1,))[0],
                        prior_ent=acc[5], post_ent=acc[6])
         bt = lambda x: x.transpose(0, 1)
-        if gauss:
-            post = {"stoch": bt(out["post_stoch"]), "deter": bt(out["deter"]), "mean": bt(out["post_mean"]),
-                    "std": bt(out["post_std"])}
-        else:
-            post = {"stoch": bt(out["post_stoch"]), "deter": bt(out["deter"]), "logit": bt(out["post_logit"])}
+        post = dyn._state(out, "post", bt)
         self._last = dict(out=out, embed=embed.view(T, B, E_), kl=kl, ent_post=ent_p, action_tm=out["action"])
         context = _LazyContext(self, post)
         rng.commit()

@@ -224,16 +224,29 @@ class RSSM(nn.Module):
         ops.gemm(x2, lin.weight, out, bias=lin.bias)
         return {"logit": out.reshape(tuple(lead) + (self._stoch, self._discrete))}
 
+    @property
+    def _stat_keys(self):
+        """The statistics a state of this latent kind carries beside "stoch" and "deter"."""
+        return ("logit",) if self._discrete else ("mean", "std")
+
+    def _state(self, src, kind=None, f=lambda x: x):
+        """The state dict {"stoch", "deter", *_stat_keys} out of `src`: the buffer dict of one step, or (kind = "post" /
+        "prior") the time-major outputs of the observe scan, whose entries are "<kind>_stoch", "deter", "<kind>_<stat>".
+        f is applied to every entry (batch-major views or copies of the scan's buffers)."""
+        pre = kind + "_" if kind else ""
+        return {"stoch": f(src[pre + "stoch"]), "deter": f(src["deter"]),
+                **{k: f(src[pre + k]) for k in self._stat_keys}}
+
     def _step_bufs(self, M, dev):
         S, D, De, Hd = self._stoch, self._discrete, self._deter, self._hidden
         mk = lambda *s: torch.empty(*s, device=dev)
+        b = dict(x1pre=mk(M, Hd), m1=mk(M), r1=mk(M), x1=mk(M, Hd), gpre=mk(M, 3 * De), mg=mk(M), rg=mk(M),
+                 deter=mk(M, De), x2pre=mk(M, Hd), m2=mk(M), r2=mk(M), x2=mk(M, Hd))
         if not D:
-            return dict(x1pre=mk(M, Hd), m1=mk(M), r1=mk(M), x1=mk(M, Hd), gpre=mk(M, 3 * De), mg=mk(M), rg=mk(M),
-                        deter=mk(M, De), x2pre=mk(M, Hd), m2=mk(M), r2=mk(M), x2=mk(M, Hd), raw=mk(M, 2 * S),
-                        mean=mk(M, S), std=mk(M, S), stoch=mk(M, S), eps=mk(M, S))
-        return dict(x1pre=mk(M, Hd), m1=mk(M), r1=mk(M), x1=mk(M, Hd), gpre=mk(M, 3 * De), mg=mk(M), rg=mk(M),
-                    deter=mk(M, De), x2pre=mk(M, Hd), m2=mk(M), r2=mk(M), x2=mk(M, Hd), logit=mk(M, S, D),
-                    stoch=mk(M, S, D))
+            b.update(raw=mk(M, 2 * S), mean=mk(M, S), std=mk(M, S), stoch=mk(M, S), eps=mk(M, S))
+        else:
+            b.update(logit=mk(M, S, D), stoch=mk(M, S, D))
+        return b
 
     def _gauss_head(self, x, lin, *, mode, noise=None):
         """Stat layer + its activations + the sample (or the mean) of the resulting Normal: x [..., hidden] ->
@@ -285,9 +298,7 @@ class RSSM(nn.Module):
                                  prev_action.to(torch.float32).contiguous(), b, noise=noise,
                                  rng=self._rng(), sample=sample)
         self._rng().commit()
-        if not self._discrete:
-            return {"stoch": b["stoch"], "deter": b["deter"], "mean": b["mean"], "std": b["std"]}
-        return {"stoch": b["stoch"], "deter": b["deter"], "logit": b["logit"]}
+        return self._state(b)
 
     def obs_step(self, prev_state, prev_action, embed, is_first, sample=True, noise=None, prior=True):
         """networks.py:174-206 (branch-free reset; no host sync on is_first).
@@ -316,11 +327,11 @@ class RSSM(nn.Module):
             x = self._obs_out_layers(torch.cat([pri["deter"], embed.to(torch.float32)], -1))
             if not D:
                 stats, stoch = self._gauss_head(x, self._obs_stat_layer, mode=not sample, noise=nz.get("post"))
-                return {"stoch": stoch, "deter": pri["deter"], **stats}, (pri if prior else None)
-            logit = self._suff_stats_layer("obs", x)["logit"]
-            dist = tools.OneHotDist(logit, unimix_ratio=self._unimix_ratio, rng=self._rng())
-            stoch = dist.sample(noise=nz.get("post")) if sample else dist.mode()
-            return {"stoch": stoch, "deter": pri["deter"], "logit": logit}, (pri if prior else None)
+            else:
+                stats = self._suff_stats_layer("obs", x)
+                dist = tools.OneHotDist(stats["logit"], unimix_ratio=self._unimix_ratio, rng=self._rng())
+                stoch = dist.sample(noise=nz.get("post")) if sample else dist.mode()
+            return self._state(dict(stats, stoch=stoch, deter=pri["deter"])), (pri if prior else None)
         s0, d0 = self.engine.init_state_fwd()
         first = is_first.to(torch.float32).reshape(B).contiguous()
         sin, din, ain = torch.empty(B, SD, device=dev), torch.empty(B, De, device=dev), torch.empty(B, A, device=dev)
@@ -338,24 +349,20 @@ class RSSM(nn.Module):
         self.engine.img_step_fwd(sin, din, ain, b, noise=nz.get("prior"), rng=self._rng(), sample=sample, head=prior)
         x3pre, x3 = torch.empty(B, Hd, device=dev), torch.empty(B, Hd, device=dev)
         E.dense_ln_fwd(p.obs_out, b["deter"], embed.contiguous(), x3pre, None, None, x3)
+        prior = self._state(b) if prior else None
         if not D:
-            prior = {"stoch": b["stoch"], "deter": b["deter"], "mean": b["mean"], "std": b["std"]} if prior else None
             raw = torch.empty(B, 2 * S, device=dev)
             ops.gemm(x3, p.obs.W, raw, bias=p.obs.b)
-            mean, std, stoch = (torch.empty(B, S, device=dev) for _ in range(3))
-            ops.gauss_head_fwd(raw, stoch, mean, std, eps=nz.get("post"), rng=self._rng(), mode=not sample,
-                               **self._head_kw())
-            self._rng().commit()
-            return {"stoch": stoch, "deter": b["deter"], "mean": mean, "std": std}, prior
-        prior = {"stoch": b["stoch"], "deter": b["deter"], "logit": b["logit"]} if prior else None
-        logit = torch.empty(B, S, D, device=dev)
-        ops.gemm(x3, p.obs.W, logit.view(B, SD), bias=p.obs.b)
-        stoch = torch.empty(B, S, D, device=dev)
-        ops.onehot_sample(logit, stoch, noise=nz.get("post"), rng=self._rng(), unimix=self._unimix_ratio,
-                          mode=not sample)
+            q = {k: torch.empty(B, S, device=dev) for k in ("stoch", "mean", "std")}
+            ops.gauss_head_fwd(raw, q["stoch"], q["mean"], q["std"], eps=nz.get("post"), rng=self._rng(),
+                               mode=not sample, **self._head_kw())
+        else:
+            q = {k: torch.empty(B, S, D, device=dev) for k in ("stoch", "logit")}
+            ops.gemm(x3, p.obs.W, q["logit"].view(B, SD), bias=p.obs.b)
+            ops.onehot_sample(q["logit"], q["stoch"], noise=nz.get("post"), rng=self._rng(), unimix=self._unimix_ratio,
+                              mode=not sample)
         self._rng().commit()
-        post = {"stoch": stoch, "deter": b["deter"], "logit": logit}
-        return post, prior
+        return self._state(dict(q, deter=b["deter"])), prior
 
     def observe(self, embed, action, is_first, state=None, noise=None):
         """networks.py:127-143: embed [B,T,E], action [B,T,A], is_first [B,T] -> (post, prior) of [B,T,...]."""
@@ -367,20 +374,12 @@ class RSSM(nn.Module):
             tmg = lambda x: x.to(torch.float32).transpose(0, 1).contiguous()
             dims = dict(stoch=self._stoch, discrete=self._discrete, deter=self._deter, hidden=self._hidden,
                         num_actions=self._num_actions, embed=self._embed, unimix=self._unimix_ratio, **self._head_kw())
-            if not self._discrete:
-                ps, pm, psd, dt, qs, qm, qsd = AG.ObserveGaussFn.apply(
-                    tmg(embed), tmg(action), tmg(is_first), nz.get("q_prior"), nz.get("q_post"), self._rng(), dims,
-                    *self._all_params())
-                self._rng().commit()
-                bt = lambda x: x.transpose(0, 1)
-                return ({"stoch": bt(ps), "deter": bt(dt), "mean": bt(pm), "std": bt(psd)},
-                        {"stoch": bt(qs), "deter": bt(dt), "mean": bt(qm), "std": bt(qsd)})
-            ps, pl, dt, qs, ql = AG.ObserveFn.apply(tmg(embed), tmg(action), tmg(is_first), nz.get("q_prior"),
-                                                   nz.get("q_post"), self._rng(), dims, *self._all_params())
+            fn = AG.ObserveFn if self._discrete else AG.ObserveGaussFn
+            out = dict(zip(fn.KEYS, fn.apply(tmg(embed), tmg(action), tmg(is_first), nz.get("q_prior"),
+                                             nz.get("q_post"), self._rng(), dims, *self._all_params())))
             self._rng().commit()
             bt = lambda x: x.transpose(0, 1)
-            return ({"stoch": bt(ps), "deter": bt(dt), "logit": bt(pl)},
-                    {"stoch": bt(qs), "deter": bt(dt), "logit": bt(ql)})
+            return self._state(out, "post", bt), self._state(out, "prior", bt)
         if state is not None and AG.wants_grad(embed, *self._all_params()):
             # carried state (rare with gradients): step by step through obs_step's autograd chain
             swap = lambda x: x.transpose(0, 1)
@@ -397,12 +396,7 @@ class RSSM(nn.Module):
                                       q_post=nz.get("q_post"), rng=self._rng(), state0=state0)
         self._rng().commit()
         bt = lambda x: x.transpose(0, 1).clone()
-        if not self._discrete:
-            return tuple({"stoch": bt(out[k + "_stoch"]), "deter": bt(out["deter"]), "mean": bt(out[k + "_mean"]),
-                          "std": bt(out[k + "_std"])} for k in ("post", "prior"))
-        post = {"stoch": bt(out["post_stoch"]), "deter": bt(out["deter"]), "logit": bt(out["post_logit"])}
-        prior = {"stoch": bt(out["prior_stoch"]), "deter": bt(out["deter"]), "logit": bt(out["prior_logit"])}
-        return post, prior
+        return self._state(out, "post", bt), self._state(out, "prior", bt)
 
     def imagine_with_action(self, action, state, noise=None):
         """networks.py:145-152: open-loop rollout of given actions [B,T,A] from `state` {[B,...]}.
