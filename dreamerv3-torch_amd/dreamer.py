@@ -163,7 +163,8 @@ class Dreamer(nn.Module):
             self._stager = BatchStager(self._config.device)
             models.share_runner(self._wm, self._runner)  # (WorldModel._train / ImagBehavior._train share it)
             # the metrics of a phase are added up right behind its optimizer graph, on the stream that graph ran on
-            self._runner.metric_sinks = (lambda m: self._accumulate(m, "wm"), lambda m: self._accumulate(m, "beh"))
+            self._runner.metric_sinks = (lambda m: self._accumulate(m, "wm"), lambda m: self._accumulate(m, "beh"),
+                                         lambda m: self._accumulate({"expl_" + k: v for k, v in m.items()}, "expl"))
         host = all(not isinstance(v, torch.Tensor) for v in data.values())
         explorer = self._expl_behavior is not self._task_behavior
         pipelined = pipelined and not explorer and bool(getattr(self._config, "pipeline_updates", True))
@@ -171,12 +172,17 @@ class Dreamer(nn.Module):
         with torch.cuda.stream(self._runner.launch_stream() or torch.cuda.current_stream()):
             staged = (self._stager.stage(data) if host else
                       {k: (v if k == "image" else v.to(torch.float32)) for k, v in data.items()})
-            (self._runner.step_pipelined if pipelined else self._runner.step)(staged)
-            if explorer:
-                # dreamer.py:201-203: the explorer trains on the same posterior states (eagerly: its objective runs torch
-                # autograd, which a hipGraph segment cannot hold)
-                xm = self._expl_behavior.train(self._runner.last_post, self._runner.last_context,
-                                               self._runner.last_data)[-1]
+            xb, r = self._expl_behavior, self._runner
+            fused = explorer and isinstance(xb, expl.Plan2Explore) and xb.fused()
+            if fused:
+                # Plan2Explore with expl_fused: an explicit forward / backward on the member-batched kernels that the
+                # runner captures and replays behind the task behaviour (its metrics come through the third sink)
+                r.attach_explorer(xb)
+            (r.step_pipelined if pipelined else r.step)(staged)
+            if explorer and not fused:
+                # dreamer.py:201-203: the explorer trains on the same posterior states (eagerly: `train`'s objective runs
+                # torch autograd, which a hipGraph segment cannot hold)
+                xm = xb.train(r.last_post, r.last_context, r.last_data)[-1]
                 self._accumulate({"expl_" + k: v for k, v in xm.items()}, "expl")
 
     def state_dict(self, *args, **kwargs):

@@ -1312,3 +1312,137 @@ class ConvDecoderEngine:
         k1 = x1.shape[1]
         ops.gemm(dh0, self.lin.W[:, :k1], dx1, transB=False, accumulate=acc_dx)
         ops.gemm(dh0, self.lin.W[:, k1:], dx2, transB=False, accumulate=acc_dx)
+
+
+# ---------------------------------------------------------------------------------------------
+# Plan2Explore's ensemble (exploration.py:40-135): K MLPs with a tanh-mean Normal head on one shared input
+# ---------------------------------------------------------------------------------------------
+class EnsembleEngine:
+    """The `disag_models` members as stacked tensors: every layer of all members is one launch (csrc/ensops.hip).
+
+    bucket: the explorer's ParamBucket built with members=K over the members' parameters in nn.ModuleList order, each
+    member's as networks.MLP registers them ([Linear W, LayerNorm weight, LayerNorm bias] x layers, mean_layer W, b).
+    The stacked [K, ...] tensors are views of the bucket's flat buffers (ParamBucket.stacked), i.e. the same storage as
+    the modules' parameters and their .grad.  Activations are [K][M][U] workspace buffers keyed by the row count, so the
+    replay batch (regress_fwd_bwd) and the imagined rows (disag_fwd / disag_bwd) do not share any."""
+
+    def __init__(self, name: str, bucket, layers: int, ws: Workspace, *, std: float, scale: float = 1.0, log: bool = True):
+        if bucket.members < 2 or layers < 1:
+            raise ValueError("EnsembleEngine: needs at least 2 members (the unbiased std) and 1 trunk layer")
+        self.name, self.bucket, self.L, self.ws = name, bucket, int(layers), ws
+        self.K = bucket.members
+        self.std, self.scale, self.log = float(std), float(scale), bool(log)
+        self._kept = None  # (x, have_mu) of the last disag_fwd
+        # scratch of ops.ens_regress_loss, zeroed ONCE: the kernel resets its own ticket
+        self._loss_ws = torch.zeros(ops.ENS_LOSS_WS, dtype=F32, device=ws.device)
+
+    # stacked parameter / gradient views (taken per call: the bucket may have been rebuilt by Module.to())
+    def _params(self):
+        st = self.bucket.stacked
+        layers = [(st(3 * i), st(3 * i + 1), st(3 * i + 2)) for i in range(self.L)]
+        return layers, st(3 * self.L), st(3 * self.L + 1)
+
+    def _acts(self, M: int, tag: str):
+        layers, _, _ = self._params()
+        ws, nm, K = self.ws, f"{self.name}.{tag}", self.K
+        acts = []
+        for i, ((W, _), _, _) in enumerate(layers):
+            U = W.shape[1]
+            acts.append((ws.get(f"{nm}.pre{i}", (K, M, U)), ws.get(f"{nm}.m{i}", (K * M,)),
+                         ws.get(f"{nm}.r{i}", (K * M,)), ws.get(f"{nm}.y{i}", (K, M, U))))
+        return acts
+
+    def _trunk_fwd(self, x, tag: str):
+        """x [M, F] (shared by all members) -> h [K][M][U]."""
+        layers, _, _ = self._params()
+        acts = self._acts(x.shape[0], tag)
+        h = x
+        for ((W, _), (g, _), (b, _)), (pre, mean, rstd, y) in zip(layers, acts):
+            ops.ens_gemm(h, W, pre)
+            ops.ens_ln_act_fwd(pre, g, b, y, mean, rstd)
+            h = y
+        return h, acts
+
+    def _trunk_bwd(self, x, acts, dh, tag: str, *, wgrad: bool, dx=None, cols=None):
+        """dh [K][M][U] (read only) = gradient on the trunk output -> parameter gradients accumulated into the bucket
+        (wgrad) and dx [M, F] = the sum over members of the first layer's data gradient (fixed order)."""
+        layers, _, _ = self._params()
+        ws, nm, K, M = self.ws, f"{self.name}.{tag}", self.K, x.shape[0]
+        dy = dh
+        for i in reversed(range(self.L)):
+            (W, gW), (g, gg), (b, gb) = layers[i]
+            pre, mean, rstd, _ = acts[i]
+            dpre = ws.get(f"{nm}.dpre{i}", tuple(pre.shape))
+            ops.ens_ln_act_bwd(dy, pre, g, b, mean, rstd, dpre, gg if wgrad else None, gb if wgrad else None)
+            if wgrad:
+                ops.ens_gemm(dpre, acts[i - 1][3] if i > 0 else x, gW, transA=True, transB=False, accumulate=True)
+            if i > 0:
+                dprev = ws.get(f"{nm}.dy{i - 1}", tuple(acts[i - 1][3].shape))
+                ops.ens_gemm(dpre, W, dprev, transB=False)
+                dy = dprev
+            elif dx is not None:
+                ops.ens_gemm(dpre, W if cols is None else W[:, :, cols], dx, transB=False)
+
+    # -- public surface ---------------------------------------------------------------------------
+    def forward(self, x):
+        """x [M, F] -> mu [K, M, W] = tanh(mean_layer_k(trunk_k(x))) (the mode of member k's Normal head)."""
+        _, (Wh, _), (bh, _) = self._params()
+        M = x.shape[0]
+        h, _ = self._trunk_fwd(x, f"f{M}")
+        mu = self.ws.get(f"{self.name}.f{M}.mu", (self.K, M, Wh.shape[1]))
+        ops.ens_gemm(h, Wh, mu, bias=bh)
+        ops.tanh_fwd(mu, mu)
+        return mu
+
+    def regress_fwd_bwd(self, x, target):
+        """Ensemble regression (Plan2Explore._train_ensemble): x [M, F], target [M, W] -> loss (device scalar, a
+        workspace buffer); gradients are ACCUMULATED into the bucket's .grad (the caller zeroed it)."""
+        _, (Wh, gWh), (bh, gbh) = self._params()
+        M, ws, nm = x.shape[0], self.ws, f"{self.name}.t{x.shape[0]}"
+        h, acts = self._trunk_fwd(x, f"t{M}")
+        pre = ws.get(f"{nm}.out", (self.K, M, Wh.shape[1]))
+        ops.ens_gemm(h, Wh, pre, bias=bh)
+        loss = ws.get(f"{nm}.loss", (1,))
+        ops.ens_regress_loss(pre, target, pre, loss, self._loss_ws, self.std)  # pre <- d loss / d pre
+        ops.ens_gemm(pre, h, gWh, transA=True, transB=False, accumulate=True)
+        ops.ens_colsum(pre, gbh, accumulate=True)
+        dh = ws.get(f"{nm}.dh", tuple(h.shape))
+        ops.ens_gemm(pre, Wh, dh, transB=False)
+        self._trunk_bwd(x, acts, dh, f"t{M}", wgrad=True)
+        return loss.view(())
+
+    def disag_fwd(self, x, reward=None, *, keep: bool = True):
+        """x [M, F] -> reward [M, 1] = scale * f(mean_d std_k mu_k[m, d]).  keep: also store the members' predictions
+        (what disag_bwd needs; pass False when no gradient will flow through the reward, imag_gradient "reinforce")."""
+        _, (Wh, _), (bh, _) = self._params()
+        M, W, ws, nm = x.shape[0], Wh.shape[1], self.ws, f"{self.name}.d{x.shape[0]}"
+        h, _ = self._trunk_fwd(x, f"d{M}")
+        if reward is None:
+            reward = ws.get(f"{nm}.reward", (M, 1))
+        mu = ws.get(f"{nm}.mu", (self.K, M, W)) if keep else None
+        ops.ens_disag_fwd(h, Wh, bh, reward, ws.get(f"{nm}.disag", (M,)), ws.get(f"{nm}.part", (-(-W // 64) * M,)),
+                          mu=mu, scale=self.scale, log=self.log)
+        self._kept = (x, keep)
+        return reward
+
+    def disag_bwd(self, dreward, dx=None, cols=None):
+        """dreward [M] or [M, 1] = d objective / d reward of the last disag_fwd(x, keep=True) -> dx [M, F], or only its
+        columns `cols` (a slice: the action columns are all the behaviour needs).  No parameter gradient: the ensemble
+        is not trained through the reward.  Consumes the kept predictions: one backward per forward."""
+        if self._kept is None or not self._kept[1]:
+            raise RuntimeError("EnsembleEngine.disag_bwd: no kept predictions (disag_fwd(keep=True) first)")
+        x = self._kept[0]
+        M = x.shape[0]
+        _, (Wh, _), _ = self._params()
+        ws, nm = self.ws, f"{self.name}.d{M}"
+        mu = ws.get(f"{nm}.mu", (self.K, M, Wh.shape[1]))
+        ops.ens_disag_bwd(mu, ws.get(f"{nm}.disag", (M,)), dreward, scale=self.scale, log=self.log)  # mu <- d / d pre
+        self._kept = None
+        acts = self._acts(M, f"d{M}")
+        dh = ws.get(f"{nm}.dh", tuple(acts[-1][3].shape))
+        ops.ens_gemm(mu, Wh, dh, transB=False)
+        if dx is None:
+            width = x.shape[1] if cols is None else len(range(*cols.indices(x.shape[1])))
+            dx = ws.get(f"{nm}.dx", (M, width))
+        self._trunk_bwd(x, acts, dh, f"d{M}", wgrad=False, dx=dx, cols=cols)
+        return dx

@@ -306,6 +306,8 @@ class UpdateRunner:
         self._calls = 0
         self._static: Dict[str, torch.Tensor] = {}
         self._g_wm = self._g_beh = None  # (per-lane graphs of the forward/backward, optimizer graph); (behaviour, optimizers)
+        # an explorer with an explicit update (exploration.Plan2Explore, fused path; attach_explorer) and its three graphs
+        self.expl, self._g_expl, self._m3 = None, None, {}
         self._cap = {}  # what the captured halves returned (static tensors the replays rewrite)
         self._pool = torch.cuda.graph_pool_handle() if torch.cuda.is_available() else None
         self._m1, self._m2, self._beh_out = {}, {}, None
@@ -404,8 +406,48 @@ class UpdateRunner:
         self._beh_out, self._m2 = self._cap["beh_out"], self._cap["beh_out"][-1]
         self._sink(1, self._m2)
 
+    # Explorer half (Plan2Explore on the member-batched kernels): [ensemble regression fwd+bwd] -> all-reduce ->
+    # [ensemble clip+Adam, exploration behaviour fwd+bwd on the UPDATED members' disagreement] -> all-reduce x2 ->
+    # [clip+Adam x2].  Three graphs, the three collectives between them outside capture.
+    def attach_explorer(self, expl):
+        """expl: an object with train_regress / train_behave / train_opt (exploration.Plan2Explore) that step() trains
+        on the posterior of the world-model half, after the task behaviour."""
+        if expl is not self.expl:
+            self.expl, self._g_expl = expl, None
+
+    def _expl_half(self, eager=False):
+        x = self.expl
+        if self._replaying(eager) and self._g_expl is None:
+            torch.cuda.synchronize()
+            try:
+                self._capture_expl()
+            except CaptureRefused as e:
+                self._refused(e)
+        if not self._replaying(eager):
+            x.train_fwd_bwd(self.last_post, self.last_context, self.last_data)
+            self._m3 = x.train_opt()[-1]
+            self._sink(2, self._m3)
+            return
+        gr, gb, go = self._g_expl
+        gr.replay()
+        x._expl_opt.bucket.allreduce()
+        gb.replay()
+        x._behavior._actor_opt.bucket.allreduce()
+        x._behavior._value_opt.bucket.allreduce()
+        go.replay()
+        self._m3 = self._cap["expl_out"][-1]
+        self._sink(2, self._m3)
+
+    def _capture_expl(self):
+        x = self.expl
+        gr, gb, go = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+        _capture(gr, lambda: x.train_regress(self.last_post, self.last_context, self.last_data), pool=self._pool)
+        _capture(gb, lambda: x.train_behave(self.last_post, allreduce=False), pool=self._pool)
+        _capture(go, lambda: self._cap.update(expl_out=x.train_opt(allreduce=False)), pool=self._pool)
+        self._g_expl = (gr, gb, go)
+
     def _sink(self, which, metrics):
-        if self.metric_sinks is not None and self.metric_sinks[which] is not None:
+        if self.metric_sinks is not None and len(self.metric_sinks) > which and self.metric_sinks[which] is not None:
             self.metric_sinks[which](metrics)
 
     def _model_cut(self):
@@ -427,22 +469,26 @@ class UpdateRunner:
         import sys
 
         print(f"[dv3hip] hipGraph capture refused ({e}); falling back to eager launches", file=sys.stderr)
-        self.use_graph, self._g_wm, self._g_beh = False, None, None
+        self.use_graph, self._g_wm, self._g_beh, self._g_expl = False, None, None, None
         torch.cuda.synchronize()  # an asynchronous HIP error surfaces here instead of being trained over
 
     def close(self):
         """Drop every captured graph (engine.Lanes calls this before it destroys the streams they were captured on)."""
-        self._g_wm = self._g_beh = self._pipe = None
+        self._g_wm = self._g_beh = self._g_expl = self._pipe = None
         self._cap, self._beh_out = {}, None
         self._pipe_pending = False
         self.use_graph = False
 
     def _check_weights(self):
-        """The captured launches hold raw pointers into the three flat parameter buckets: replaying them over weights
-        that have been moved since (Module.to, a rebuilt bucket) would train memory nobody reads."""
-        where = tuple(b.flat.data_ptr() if b.settled() else 0 for b in
-                      (self.wm._model_opt.bucket, self.beh._actor_opt.bucket, self.beh._value_opt.bucket))
-        if self._g_wm is None:
+        """The captured launches hold raw pointers into the flat parameter buckets (the world model's, the task
+        behaviour's two and, with an explorer attached, its three): replaying them over weights that have been moved
+        since (Module.to, a rebuilt bucket) would train memory nobody reads."""
+        buckets = [self.wm._model_opt.bucket, self.beh._actor_opt.bucket, self.beh._value_opt.bucket]
+        if self.expl is not None and self._g_expl is not None:
+            buckets += [self.expl._expl_opt.bucket, self.expl._behavior._actor_opt.bucket,
+                        self.expl._behavior._value_opt.bucket]
+        where = tuple(b.flat.data_ptr() if b.settled() else 0 for b in buckets)
+        if self._g_wm is None or len(where) != len(getattr(self, "_weights", ())):
             self._weights = where
         elif where != self._weights:
             raise RuntimeError("the parameters were moved after the update's launch sequence was captured (Module.to / "
@@ -514,6 +560,8 @@ class UpdateRunner:
             self._wm_half(data, eager)
             self._beh_half(eager)
             self.last_metrics = {**self._m1, **self._m2}
+            if self.expl is not None:
+                self._expl_half(eager)
 
         self._on_launch_stream(both)
 

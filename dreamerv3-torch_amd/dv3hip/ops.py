@@ -1855,3 +1855,191 @@ def quantile2_ema(x, q0, q1, ema=None, alpha=0.0, out_q=None):
     _call("dv3_quantile2_ema", _ptr(x), x.numel(), float(q0), float(q1), _ptr(ema), float(alpha), _ptr(out_q), _stream())
     return out_q if out_q is not None else ema
 
+
+
+# ---------------------------------------------------------------------------------------------
+# member-batched ensemble kernels (csrc/ensops.hip): Plan2Explore's disag_models MLPs, one launch per layer
+# ---------------------------------------------------------------------------------------------
+ENS_LOSS_WS = 1025  # floats of ens_regress_loss's scratch (block partials + ticket), zeroed once by its owner
+
+
+def _ens3d(t: torch.Tensor, name: str, members: int = 0):
+    """[K][R][C] with unit inner stride, row stride >= C and any member stride that keeps the members' rows apart
+    -> (K, R, C, ld, member stride)."""
+    _f32(t, name)
+    if t.dim() != 3:
+        raise ValueError(f"{name}: need [members][rows][cols], got shape {tuple(t.shape)}")
+    K, R, C = t.shape
+    if members and K != members:
+        raise ValueError(f"{name}: {K} members, expected {members}")
+    if (C > 1 and t.stride(2) != 1) or (R > 1 and t.stride(1) < C):
+        raise ValueError(f"{name}: need unit inner stride and row stride >= cols, got strides {t.stride()}")
+    ld = t.stride(1) if R > 1 else max(C, 1)
+    st = t.stride(0) if K > 1 else (R - 1) * ld + C
+    if K > 1 and st < (R - 1) * ld + C:
+        raise ValueError(f"{name}: members overlap (member stride {st})")
+    return K, R, C, ld, st
+
+
+def _ens2d(t: torch.Tensor, name: str, members: int, cols: int) -> int:
+    """[K][C] per-member vectors (LayerNorm gamma / beta, head bias) -> member stride."""
+    _f32(t, name)
+    if t.dim() != 2 or tuple(t.shape) != (members, cols) or (cols > 1 and t.stride(1) != 1):
+        raise ValueError(f"{name}: need [{members}][{cols}] with unit inner stride, got {tuple(t.shape)} {t.stride()}")
+    st = t.stride(0) if members > 1 else cols
+    if st < cols:
+        raise ValueError(f"{name}: members overlap")
+    return st
+
+
+def ens_gemm(A, B, C, *, bias=None, transA=False, transB=True, accumulate=False):
+    """C_k (+)= op(A_k) op(B_k) + bias_k for every member k in ONE launch.  A, B: [K][.][.] or a 2-D matrix shared by
+    all members; C: [K][M][N], or 2-D [M][N] = the sum over members (fixed order).  transA / transB as ops.gemm."""
+    if transA and transB:
+        raise ValueError("ens_gemm: transA and transB together are not supported")
+    Kb = max(t.shape[0] if t.dim() == 3 else 0 for t in (A, B, C))
+    if Kb <= 0:
+        raise ValueError("ens_gemm: one of A, B, C must be member-stacked ([K][.][.])")
+
+    def _mat(t, name):
+        if t.dim() == 2:
+            r, c, ld = _rows2d(t, name)
+            return r, c, ld, 0
+        _, r, c, ld, st = _ens3d(t, name, Kb)
+        return r, c, ld, st
+
+    ra, ca, lda, sA = _mat(A, "A")
+    rb, cb, ldb, sB = _mat(B, "B")
+    mc, nc, ldc, sC = _mat(C, "C")
+    M, K = (ca, ra) if transA else (ra, ca)
+    N, Kb_ = (rb, cb) if transB else (cb, rb)
+    if K != Kb_ or K <= 0:
+        raise ValueError(f"ens_gemm: reduction sizes differ ({K} vs {Kb_})")
+    if (mc, nc) != (M, N):
+        raise ValueError(f"ens_gemm: C is {mc}x{nc}, expected {M}x{N}")
+    sBias = _ens2d(bias, "bias", Kb, N) if bias is not None else 0
+    kind = f"tA={int(transA)},tB={int(transB)}" + (",sum" if sC == 0 else "")
+    _call("dv3_ens_gemm_f32", Kb, int(transA), int(transB), M, N, K, _ptr(A), lda, sA, _ptr(B), ldb, sB, _ptr(C), ldc,
+          sC, _ptr(bias), sBias, int(accumulate), _stream(),
+          key=f"ens_gemm_kernel<{kind}>" + (f"[{Kb}x{M}x{N}x{K}]" if PROFILE.by_shape else ""),
+          flops=2.0 * Kb * M * N * K,
+          nbytes=4.0 * ((Kb if sA else 1) * M * K + Kb * N * K + (Kb if sC else 1) * M * N))
+    return C
+
+
+def ens_ln_act_fwd(x, gamma, beta, y, mean, rstd):
+    """SiLU(LayerNorm(x_k) * gamma_k + beta_k) over [K][M][N]; mean / rstd [K*M] saved for the backward."""
+    K, M, N, ldx, sx = _ens3d(x, "x")
+    _, My, Ny, ldy, sy = _ens3d(y, "y", K)
+    if (My, Ny) != (M, N) or sx != M * ldx or sy != M * ldy:
+        raise ValueError("ens_ln_act_fwd: x / y must be [K][M][N] with the members' rows back to back")
+    sG = _ens2d(gamma, "gamma", K, N)
+    if _ens2d(beta, "beta", K, N) != sG:
+        raise ValueError("ens_ln_act_fwd: gamma and beta need the same member stride")
+    _contig(mean, "mean"), _contig(rstd, "rstd")
+    if mean.numel() != K * M or rstd.numel() != K * M or N > 2048:
+        raise ValueError("ens_ln_act_fwd: statistics size mismatch or N > 2048")
+    _call("dv3_ens_ln_act_fwd", _ptr(x), ldx, _ptr(gamma), _ptr(beta), sG, _ptr(y), ldy, _ptr(mean), _ptr(rstd), K, M,
+          N, _stream(), key="dv3_ens_ln_act_fwd" + (f"[{K}x{M}x{N}]" if PROFILE.by_shape else ""),
+          nbytes=8.0 * K * M * N)
+    return y
+
+
+def ens_ln_act_bwd(dy, x, gamma, beta, mean, rstd, dx, dgamma=None, dbeta=None):
+    """Backward of ens_ln_act_fwd; dgamma / dbeta [K][N] are accumulated (atomic adds).  dx must not alias dy."""
+    K, M, N, ldx, sx = _ens3d(x, "x")
+    strides = []
+    for t, nm in ((dy, "dy"), (dx, "dx")):
+        _, Mt, Nt, ldt, st = _ens3d(t, nm, K)
+        if (Mt, Nt) != (M, N) or st != M * ldt:
+            raise ValueError(f"ens_ln_act_bwd: {nm} must be [K][M][N] with the members' rows back to back")
+        strides.append(ldt)
+    if sx != M * ldx or dx.data_ptr() == dy.data_ptr():
+        raise ValueError("ens_ln_act_bwd: x layout, or dx aliases dy")
+    sG = _ens2d(gamma, "gamma", K, N)
+    if _ens2d(beta, "beta", K, N) != sG:
+        raise ValueError("ens_ln_act_bwd: gamma and beta need the same member stride")
+    if (dgamma is None) != (dbeta is None):
+        raise ValueError("dgamma/dbeta: both or neither")
+    if dgamma is not None and (_ens2d(dgamma, "dgamma", K, N) != sG or _ens2d(dbeta, "dbeta", K, N) != sG):
+        raise ValueError("ens_ln_act_bwd: dgamma / dbeta need gamma's member stride")
+    _contig(mean, "mean"), _contig(rstd, "rstd")
+    if mean.numel() != K * M or rstd.numel() != K * M or N > 2048 or K > 65535:
+        raise ValueError("ens_ln_act_bwd: size mismatch")
+    _call("dv3_ens_ln_act_bwd", _ptr(dy), strides[0], _ptr(x), ldx, _ptr(gamma), _ptr(beta), sG, _ptr(mean),
+          _ptr(rstd), _ptr(dx), strides[1], _ptr(dgamma), _ptr(dbeta), K, M, N, _stream(),
+          key="dv3_ens_ln_act_bwd" + (f"[{K}x{M}x{N}]" if PROFILE.by_shape else ""), nbytes=12.0 * K * M * N)
+    return dx
+
+
+def ens_colsum(x, out, *, accumulate=False):
+    """out_k[n] (+)= sum_m x_k[m][n]."""
+    K, M, N, ldx, sx = _ens3d(x, "x")
+    so = _ens2d(out, "out", K, N)
+    if K > 65535:
+        raise ValueError("ens_colsum: too many members")
+    _call("dv3_ens_colsum", _ptr(x), ldx, sx, _ptr(out), so, K, M, N, int(accumulate), _stream(),
+          key="dv3_ens_colsum" + (f"[{K}x{M}x{N}]" if PROFILE.by_shape else ""), nbytes=4.0 * K * M * N)
+    return out
+
+
+def ens_regress_loss(pre, target, dpre, loss, ws, std):
+    """loss[0] = -mean_k mean_m sum_d log N(target; tanh(pre_k), std), dpre = d loss / d pre (may alias pre)."""
+    _contig(pre, "pre"), _contig(dpre, "dpre"), _contig(loss, "loss"), _contig(ws, "ws")
+    if pre.dim() != 3 or dpre.shape != pre.shape:
+        raise ValueError("ens_regress_loss: pre / dpre must be contiguous [K][M][W]")
+    K, M, W = pre.shape
+    Mt, Wt, ldt = _rows2d(target, "target")
+    if (Mt, Wt) != (M, W) or loss.numel() != 1 or ws.numel() < ENS_LOSS_WS or not std > 0:
+        raise ValueError("ens_regress_loss: target / loss / ws size mismatch")
+    _call("dv3_ens_regress_loss", _ptr(pre), _ptr(target), ldt, _ptr(dpre), _ptr(loss), _ptr(ws), K, M, W, float(std),
+          _stream(), key="dv3_ens_regress_loss" + (f"[{K}x{M}x{W}]" if PROFILE.by_shape else ""),
+          nbytes=4.0 * (2 * K + 1) * M * W)
+    return loss
+
+
+def ens_disag_fwd(h, w, bias, reward, disag, part, *, mu=None, scale=1.0, log=True):
+    """reward[m] = scale * f(mean_d std_k tanh(h_k[m] w_k[d]^T + bias_k[d])), f = log or identity; disag [M] receives
+    the statistic before f.  K < 2 is rejected by the library (DV3_ERR_ARG, nothing launched).  mu ([K][M][W]): keep the members' predictions for ens_disag_bwd."""
+    K, M, U, ldh, sH = _ens3d(h, "h")
+    _, W, Uw, ldw, sW = _ens3d(w, "w", K)
+    if Uw != U:
+        raise ValueError("ens_disag_fwd: head width mismatch")
+    sBias = _ens2d(bias, "bias", K, W)
+    _contig(disag, "disag"), _contig(part, "part")
+    _f32(reward, "reward")
+    if reward.dim() == 2 and reward.shape[1] == 1:
+        ldr = reward.stride(0) if M > 1 else 1
+    elif reward.dim() == 1:
+        ldr = reward.stride(0) if M > 1 else 1
+    else:
+        raise ValueError("ens_disag_fwd: reward must be [M] or [M, 1]")
+    if reward.shape[0] != M or ldr < 1 or disag.numel() != M or part.numel() < -(-W // 64) * M:
+        raise ValueError("ens_disag_fwd: reward / disag / part size mismatch")
+    if mu is not None:
+        _contig(mu, "mu")
+        if tuple(mu.shape) != (K, M, W):
+            raise ValueError("ens_disag_fwd: mu must be [K][M][W]")
+    _call("dv3_ens_disag_fwd", _ptr(h), ldh, sH, _ptr(w), ldw, sW, _ptr(bias), sBias, _ptr(mu), _ptr(part),
+          _ptr(disag), _ptr(reward), ldr, K, M, W, U, float(scale), int(bool(log)), _stream(),
+          key="ens_disag_fwd_kernel" + ("+mu" if mu is not None else "") + (f"[{K}x{M}x{W}x{U}]" if PROFILE.by_shape else ""),
+          flops=2.0 * K * M * W * U, nbytes=4.0 * K * (M * U + W * U + (M * W if mu is not None else 0)))
+    return reward
+
+
+def ens_disag_bwd(mu, disag, dreward, *, scale=1.0, log=True):
+    """In place mu [K][M][W] -> d(sum_m dreward[m] reward[m]) / d pre_k."""
+    _contig(mu, "mu"), _contig(disag, "disag")
+    _f32(dreward, "dreward")
+    if mu.dim() != 3:
+        raise ValueError("ens_disag_bwd: mu must be [K][M][W]")
+    K, M, W = mu.shape
+    if dreward.dim() not in (1, 2) or dreward.shape[0] != M or (dreward.dim() == 2 and dreward.shape[1] != 1):
+        raise ValueError("ens_disag_bwd: dreward must be [M] or [M, 1]")
+    lddr = dreward.stride(0) if M > 1 else 1
+    if lddr < 1 or disag.numel() != M:
+        raise ValueError("ens_disag_bwd: size mismatch")
+    _call("dv3_ens_disag_bwd", _ptr(mu), _ptr(disag), _ptr(dreward), lddr, K, M, W, float(scale), int(bool(log)),
+          _stream(), key="dv3_ens_disag_bwd" + (f"[{K}x{M}x{W}]" if PROFILE.by_shape else ""),
+          nbytes=12.0 * K * M * W)
+    return mu

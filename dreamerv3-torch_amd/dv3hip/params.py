@@ -22,12 +22,17 @@ _ALIGN = 4  # floats: keep every tensor 16-byte aligned inside the bucket
 
 
 class ParamBucket:
-    def __init__(self, name: str, params: Iterable[torch.nn.Parameter], allow_cpu: bool = False, extra: int = 0):
+    def __init__(self, name: str, params: Iterable[torch.nn.Parameter], allow_cpu: bool = False, extra: int = 0,
+                 members: int = 0):
         """allow_cpu: layout + all-reduce logic on CPU tensors (multi-process gloo tests); step() still
         needs the GPU kernels.  extra: floats that ride behind the gradients through the same all-reduce (`tail`: the
         two return-normalisation EMA values travel with the critic's gradient instead of in a collective of their own);
-        they are not parameters -- clipping and Adam never see them."""
+        they are not parameters -- clipping and Adam never see them.  members: `params` are that many equally shaped
+        blocks in a row (the Plan2Explore ensemble's MLPs); the buffer is then laid out position-major -- the members'
+        copies of parameter j sit at a fixed pitch, so `stacked(j)` is ONE strided [members, ...] tensor for the
+        member-batched kernels.  `params` keeps its order: optimizer state and state_dict keys do not change."""
         self.name = name
+        self.members = int(members)
         self.params: List[torch.nn.Parameter] = [p for p in params]
         self.flat = None
         self._layout = None
@@ -64,10 +69,26 @@ class ParamBucket:
             raise RuntimeError(f"ParamBucket {self.name}: parameters must live on the GPU (got {dev}); "
                                "the MI355X hot path has no CPU implementation")
         layout, total = [], 0
-        for p in self.params:
-            n = p.numel()
-            layout.append((total, n))
-            total += (n + _ALIGN - 1) // _ALIGN * _ALIGN
+        if self.members > 1:
+            K = self.members
+            P = len(self.params) // K
+            if P * K != len(self.params) or any(self.params[i * P + j].shape != self.params[j].shape
+                                                for i in range(K) for j in range(P)):
+                raise ValueError(f"ParamBucket {self.name}: {len(self.params)} parameters are not {K} equal members")
+            layout = [None] * len(self.params)
+            self._pitch = []
+            for j in range(P):
+                n = self.params[j].numel()
+                pitch = (n + _ALIGN - 1) // _ALIGN * _ALIGN
+                self._pitch.append((total, pitch))
+                for i in range(K):
+                    layout[i * P + j] = (total + i * pitch, n)
+                total += K * pitch
+        else:
+            for p in self.params:
+                n = p.numel()
+                layout.append((total, n))
+                total += (n + _ALIGN - 1) // _ALIGN * _ALIGN
         flat = torch.zeros(total, dtype=torch.float32, device=dev)
         extra = (self._extra + _ALIGN - 1) // _ALIGN * _ALIGN
         wire = torch.zeros(total + extra, dtype=torch.float32, device=dev)  # what crosses xGMI: gradients | tail
@@ -85,6 +106,18 @@ class ParamBucket:
             self.state = torch.zeros(4, dtype=torch.float32, device=dev)  # step, sumsq, last norm, spare
             self._norm_partial = torch.zeros(1024, dtype=torch.float32, device=dev)  # ops.sumsq_ordered's scratch
         return self
+
+    def stacked(self, j: int):
+        """(parameters, gradients) of position j of every member as [members, *shape] views of the flat buffers."""
+        self.ensure()
+        off, pitch = self._pitch[j]
+        shape = tuple(self.params[j].shape)
+        strides, acc = [], 1
+        for d in reversed(shape):
+            strides.insert(0, acc)
+            acc *= d
+        view = lambda buf: torch.as_strided(buf, (self.members,) + shape, (pitch,) + tuple(strides), off)
+        return view(self.flat), view(self.grad)
 
     def numel(self) -> int:
         return sum(n for _, n in self._layout)

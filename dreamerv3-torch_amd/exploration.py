@@ -7,8 +7,15 @@ objective)` -- exactly the calls the reference's own exploration.py makes, so ei
 modules: the ensemble runs on the HIP kernels forward and backward through dv3hip.autograd, and the intrinsic reward
 enters the hand-written reverse imagination rollout through `ImagBehavior.train_fwd_bwd`'s objective hook.
 State-dict keys (`_networks.<i>.layers...`, `_behavior.*`) are the reference's.
+
+Beside that public-surface `train`, `train_fwd_bwd` + `train_opt` run the same update without torch autograd: the
+ensemble on the member-batched kernels (dv3hip.engine.EnsembleEngine: one launch per layer for all members) and the
+intrinsic reward as ImagBehavior's "ensemble disagreement" objective (models.EnsembleObjective).
 """
 from __future__ import annotations
+
+import math
+import sys
 
 import numpy as np
 import torch
@@ -58,8 +65,109 @@ class Plan2Explore(nn.Module):
             networks.MLP(inp_dim=in_size, shape=target_size, layers=config.disag_layers, units=config.disag_units,
                          act=config.act, device=config.device)
             for _ in range(config.disag_models))
+        # members= (fused path only; expl_fused False keeps the flat layout as it was): the bucket lays the members'
+        # copies of each parameter side by side (one strided tensor per layer for the member-batched kernels);
+        # parameter order, optimizer state and state_dict keys are unchanged
         self._expl_opt = tools.Optimizer("explorer", self._networks.parameters(), config.model_lr, config.opt_eps,
-                                         config.grad_clip, wd=config.weight_decay, opt=config.opt, use_amp=False)
+                                         config.grad_clip, wd=config.weight_decay, opt=config.opt, use_amp=False,
+                                         members=config.disag_models if self._wants_fused() else 0)
+        self._told = False
+
+    # -- the fused path -----------------------------------------------------------------------------------------
+    def _wants_fused(self) -> bool:
+        cfg = self._config
+        return (bool(getattr(cfg, "expl_fused", True)) and bool(cfg.dyn_discrete) and cfg.disag_models >= 2
+                and cfg.disag_layers >= 1 and cfg.disag_units <= 2048)
+
+    def fused_reason(self):
+        """None when train_fwd_bwd / train_opt can run this configuration, else why not (then `train` is the path)."""
+        cfg = self._config
+        if not bool(getattr(cfg, "expl_fused", True)):
+            return "expl_fused is off"
+        if not cfg.dyn_discrete:
+            return "continuous latents (dyn_discrete: 0)"
+        if cfg.disag_models < 2 or cfg.disag_layers < 1 or cfg.disag_units > 2048:
+            return "ensemble shape (needs >= 2 members, >= 1 layer, <= 2048 units)"
+        if self._expl_opt.bucket.members < 2:
+            return "the module was built with expl_fused off (flat explorer bucket)"
+        return None
+
+    def fused(self) -> bool:
+        why = self.fused_reason()
+        if why is not None and not self._told and bool(getattr(self._config, "expl_fused", True)):
+            print(f"[dv3hip] Plan2Explore: {why}; the explorer takes the autograd route", file=sys.stderr)
+            self._told = True
+        return why is None
+
+    def _ensemble(self):
+        """(EnsembleEngine over the explorer bucket, the objective marker handed to the behaviour)."""
+        import networks as N_
+        from dv3hip import engine as E
+
+        cfg = self._config
+        dev = next(self._networks.parameters()).device
+        ens = self.__dict__.get("_ens")
+        if ens is None or ens[0].ws.device != dev:
+            head = self._networks[0]
+            # the fixed std of networks.MLP's Normal head (networks.py:614, 693-696)
+            std = (head._max_std - head._min_std) / (1.0 + math.exp(-(float(head._std) + 2.0))) + head._min_std
+            eng = E.EnsembleEngine("p2e", self._expl_opt.bucket, cfg.disag_layers, N_._workspace(self, dev), std=std,
+                                   scale=cfg.expl_intr_scale, log=cfg.disag_log)
+            ens = (eng, models.EnsembleObjective(eng, cfg.disag_action_cond, cfg.expl_extr_scale))
+            self.__dict__["_ens"] = ens
+        return ens
+
+    def train_fwd_bwd(self, start, context, data, noise=None, allreduce=True):
+        """`train` without autograd, first half: the ensemble's regression forward / backward AND its Adam step (the
+        behaviour must see the updated members, as in `train`), then the exploration behaviour's forward / backward
+        on their disagreement.  noise: as ImagBehavior.train_fwd_bwd.  The two stages are callable one by one
+        (train_regress, train_behave): graph.UpdateRunner captures them as separate segments with the explorer
+        bucket's all-reduce between them."""
+        self.train_regress(start, context, data)
+        self.train_behave(start, noise, allreduce)
+
+    def train_regress(self, start, context, data):
+        """Ensemble regression on the replay batch: forward, loss, gradients into the explorer bucket."""
+        why = self.fused_reason()
+        if why is not None:
+            raise NotImplementedError(f"Plan2Explore.train_fwd_bwd: {why}")
+        cfg = self._config
+        eng, _ = self._ensemble()
+        stoch = start["stoch"]
+        stoch = stoch.reshape(tuple(stoch.shape[:-2]) + (stoch.shape[-2] * stoch.shape[-1],))
+        deter, off = start["deter"], cfg.disag_offset
+        # (feat = [stoch | deter], networks.py:154-159, assembled here: `context` caches what it computes lazily, and a
+        # replayed launch sequence must not depend on whether somebody has read context["feat"] before)
+        target = dict(embed=lambda: context["embed"], stoch=lambda: stoch, deter=lambda: deter,
+                      feat=lambda: torch.cat([stoch, deter], -1))[cfg.disag_target]()
+        B, T = deter.shape[0], deter.shape[1] - off
+        SD, F_ = stoch.shape[-1], stoch.shape[-1] + deter.shape[-1]
+        A = cfg.num_actions if cfg.disag_action_cond else 0
+        ws = eng.ws
+        x = ws.get("p2e.x", (B, T, F_ + A))
+        x[..., :SD].copy_(stoch[:, :T])
+        x[..., SD:F_].copy_(deter[:, :T])
+        if A:
+            act = data["action"]
+            act = act if isinstance(act, torch.Tensor) else torch.as_tensor(np.asarray(act))
+            x[..., F_:].copy_(act.to(x.device, torch.float32)[:, :T])
+        tg = ws.get("p2e.target", (B, T, target.shape[-1]))
+        tg.copy_(target[:, off:])
+        self._expl_opt.begin()
+        self._loss = eng.regress_fwd_bwd(x.view(B * T, -1), tg.view(B * T, -1))
+
+    def train_behave(self, start, noise=None, allreduce=True):
+        """The ensemble's clip + Adam step, then the exploration behaviour's forward / backward on the updated
+        members' disagreement.  allreduce=False: the caller has all-reduced the explorer bucket."""
+        # (snapshots: the loss lives in a workspace buffer, the norm in the bucket's state vector)
+        self._pending = {k: v.detach().clone() for k, v in self._expl_opt.finish(self._loss, allreduce).items()}
+        self._behavior.train_fwd_bwd(start, noise, self._ensemble()[1])
+
+    def train_opt(self, allreduce=True):
+        """Second half: the exploration actor's and critic's optimizer steps -> (None, metrics of `train`)."""
+        metrics = dict(self._pending)
+        metrics.update(self._behavior.train_opt(allreduce)[-1])
+        return None, metrics
 
     # -- one exploration update: ensemble regression on the replay batch, then the behaviour on its disagreement ----
     def train(self, start, context, data):

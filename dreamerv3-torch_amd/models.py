@@ -450,6 +450,15 @@ class _LazyContext(dict):
         return v
 
 
+class EnsembleObjective:
+    """Marker objective of ImagBehavior.train_fwd_bwd: reward = the disagreement of a Plan2Explore ensemble
+    (engine: dv3hip.engine.EnsembleEngine, which holds intr_scale and disag_log) on the imagined [stoch | deter]
+    (+ action with action_cond), plus extr_scale * the world model's reward head when extr_scale is non-zero."""
+
+    def __init__(self, engine, action_cond: bool, extr_scale: float):
+        self.engine, self.action_cond, self.extr_scale = engine, bool(action_cond), float(extr_scale)
+
+
 class ImagBehavior(nn.Module):
     def __init__(self, config, world_model, future_predictor=None):
         super().__init__()
@@ -815,10 +824,25 @@ class ImagBehavior(nn.Module):
         fidx = im["idx"].view(HN, S) if _FUSED_IMAG and not gauss else None
         use_dyn = cfg.imag_gradient in ("dynamics", "both")
         reward = g("bh.reward", (H, N))
-        custom = objective is not None and self.__dict__.get("_objective_kinds", {}).get(
+        # the third kind of objective: the disagreement of a Plan2Explore ensemble, recognised by identity (an
+        # EnsembleObjective, not a callable to probe) -- member-batched kernels forward and backward, no autograd
+        ens = objective if isinstance(objective, EnsembleObjective) else None
+        if ens is not None and gauss:
+            raise NotImplementedError("the fused ensemble objective needs discrete latents (dyn_discrete > 0)")
+        custom = ens is None and objective is not None and self.__dict__.get("_objective_kinds", {}).get(
             self._objective_key(objective)) is False
-        r_logits = obj_out = obj_leaves = None
-        if not custom:
+        r_logits = obj_out = obj_leaves = ens_x = None
+        if ens is not None:
+            F_ = SD + De
+            ens_x = g("bh.ens_x", (HN, F_ + (A if ens.action_cond else 0)))
+            ens_x[:, :SD].copy_(fs), ens_x[:, SD:F_].copy_(fd)
+            if ens.action_cond:
+                ens_x[:, F_:].copy_(action.view(HN, A))
+            ens.engine.disag_fwd(ens_x, reward.view(HN, 1), keep=use_dyn and ens.action_cond)
+            if ens.extr_scale:
+                _, r_logits, _ = reng.forward(fs, fd, idx=fidx, D=D)
+                ops.axpby(ops.disc_mode_fwd(r_logits, g("bh.extr", (H, N))), reward, ens.extr_scale, 1.0)
+        elif not custom:
             _, r_logits, _ = reng.forward(fs, fd, idx=fidx, D=D)
             ops.disc_mode_fwd(r_logits, reward)
             if objective is not None and not self._objective_is_head(objective, im, reward):
@@ -897,7 +921,17 @@ class ImagBehavior(nn.Module):
             gs, gd = g("bh.gs", (H, N, SD)), g("bh.gd", (H, N, De))
             rows = slice(N, HN)  # step 0 is the (detached) start state: no gradient there
             g_act = None
-            if custom:
+            if ens is not None:
+                # As for a foreign objective, and as in the reference: the objective sees the DETACHED feat
+                # (models.py:513-517), so the reward reaches the dynamics through the action alone -- nothing through
+                # the imagined states, nothing at all without disag_action_cond (no backward launch is issued then).
+                gs.view(HN, SD)[rows].zero_()
+                gd.view(HN, De)[rows].zero_()
+                if ens.action_cond:
+                    # d loss / d reward -> std over members / tanh -> the members' data gradients, summed into the
+                    # action columns of the shared input
+                    g_act = ens.engine.disag_bwd(dreward.view(HN, 1), cols=slice(SD + De, SD + De + A))
+            elif custom:
                 # d loss / d reward -> the objective's own graph -> gradients on the imagined stoch / deter / action
                 # (reward[0] never enters a return, so dreward[0] = 0 and row block 0 receives nothing)
                 g_st = g_dt = None

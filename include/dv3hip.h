@@ -496,6 +496,51 @@ int dv3_transpose2d(const float* src, long lds, int R, int C, float* dst, long l
 int dv3_transpose2d_many(int njobs, const unsigned long long* jobs_host, void* stream);
 int dv3_onehot_to_idx(const float* onehot, int* idx, long R, int D, void* stream);
 
+/* ---- member-batched ensemble kernels (csrc/ensops.hip) -----------------------------------------------------------
+ * Plan2Explore's ensemble (reference exploration.py:40-135): K = disag_models MLPs on one shared input.  Activations
+ * are [K][M][U], parameters are stacked per member with a member stride in floats; every entry is ONE launch (two for
+ * dv3_ens_disag_fwd) whatever K is.
+ *
+ * dv3_ens_gemm_f32: C_k[M,N] (+)= op(A_k) op(B_k) + bias_k for k < members (64x64x32 fp32 MFMA tiles, any M/N/K).
+ *   transA 0: A_k[m*lda + k]; 1: A_k[k*lda + m] (weight gradient, reduction over the batch rows).
+ *   transB 1: B_k[n*ldb + k] (y = x W^T); 0: B_k[k*ldb + n] (dx = dy W).  transA = transB = 1 is rejected.
+ *   strideA == 0: ONE shared A for all members (the first layer's input is not replicated).
+ *   strideC == 0: C = sum_k of the member products; each workgroup adds the members in ascending k in registers, so
+ *   the sum has a fixed order (no atomics).  bias may be NULL. */
+int dv3_ens_gemm_f32(int members, int transA, int transB, int M, int N, int K, const float* A, long lda,
+                     long strideA, const float* B, long ldb, long strideB, float* C, long ldc, long strideC,
+                     const float* bias, long strideBias, int accumulate, void* stream);
+/* LayerNorm(eps 1e-3) + SiLU over the members*M rows of x, row r with gamma / beta of member r / M (stride strideG).
+ * N <= 2048.  mean / rstd [members*M] are saved for the backward.  The backward ACCUMULATES dgamma / dbeta
+ * [members][N] (stride strideG; both NULL: none) with atomic adds; dx is overwritten and must not alias dy. */
+int dv3_ens_ln_act_fwd(const float* x, long ldx, const float* gamma, const float* beta, long strideG, float* y,
+                       long ldy, float* mean, float* rstd, int members, int M, int N, void* stream);
+int dv3_ens_ln_act_bwd(const float* dy, long lddy, const float* x, long ldx, const float* gamma, const float* beta,
+                       long strideG, const float* mean, const float* rstd, float* dx, long lddx, float* dgamma,
+                       float* dbeta, int members, int M, int N, void* stream);
+/* out_k[n] (+)= sum_m x_k[m][n] (the head's bias gradient), fixed summation order. */
+int dv3_ens_colsum(const float* x, long ldx, long strideX, float* out, long strideOut, int members, int M, int N,
+                   int accumulate, void* stream);
+/* Ensemble regression loss fused with its gradient.  pre / dpre: contiguous [members][M][W] (pre-tanh head outputs,
+ * may alias); target [M][W] with row stride ldt.  mu = tanh(pre);
+ *   loss[0] = -1/(members M) sum_{k,m,d} log N(target[m][d]; mu_k[m][d], std);  dpre = d loss / d pre.
+ * ws: 1025 floats, zeroed ONCE by the caller (block partials + a ticket the kernel resets); the partials are added in
+ * block order by the last workgroup, so the scalar is reproducible. */
+int dv3_ens_regress_loss(const float* pre, const float* target, long ldt, float* dpre, float* loss, float* ws,
+                         int members, int M, int W, float std, void* stream);
+/* Disagreement reward: reward[m*ldr] = scale * f(disag[m]), disag[m] = mean_d std_k tanh(h_k[m] w_k[d]^T + bias_k[d])
+ * with the unbiased std over the members (members < 2: DV3_ERR_ARG, nothing launched); f = log when use_log.
+ * h [K][M][U] (ldh, strideH), w [K][W][U] (ldw, strideW), bias [K][W] (strideBias).  A workgroup loops over the
+ * members of its 64x64 output tile with running moments in registers; the predictions are written to
+ * mu [K][M][W] (contiguous) only when mu != NULL (kept for dv3_ens_disag_bwd).  part: ceil(W/64) * M floats of
+ * scratch; disag [M] receives the statistic before f. */
+int dv3_ens_disag_fwd(const float* h, long ldh, long strideH, const float* w, long ldw, long strideW,
+                      const float* bias, long strideBias, float* mu, float* part, float* disag, float* reward,
+                      long ldr, int members, int M, int W, int U, float scale, int use_log, void* stream);
+/* In place mu [K][M][W] -> d(sum_m dreward[m*lddr] reward[m]) / d pre_k (through std, mean, f and tanh). */
+int dv3_ens_disag_bwd(float* mu, const float* disag, const float* dreward, long lddr, int members, int M, int W,
+                      float scale, int use_log, void* stream);
+
 /* ---- compute-unit partitioned streams (csrc/streams.hip) --------------------------------------------------------
  * The MI355X-native counterpart of nothing in the reference (its update is one stream of ATen launches,
  * models.py:105-169): the reverse observe scan and the weight gradients that nothing reads before the optimizer run
