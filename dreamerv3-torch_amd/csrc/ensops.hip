@@ -401,6 +401,47 @@ __global__ __launch_bounds__(256) void ens_disag_bwd_kernel(float* __restrict__ 
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Row packing: dst[m][off_i : off_i + w_i] = src_i[m][:] for up to three row-strided sources, off_i = the running sum
+// of the widths (the ensemble's shared input [stoch | deter | action] and its regression target, assembled from
+// slices of the posterior / the imagined trajectory in ONE launch).  Flat over M * (units per row): a source whose
+// rows can be moved as 16-byte vectors (base, row strides, width and destination offset all multiples of 4 floats:
+// decided by the host, vec[i]) contributes w_i / 4 units per row, any other source w_i dword units.
+// ------------------------------------------------------------------------------------------------
+struct EnsPackParams {
+  const float* src[3];
+  long ld[3];
+  int off[3];    // first destination column of source i
+  int units[3];  // units per row of source i (0: absent)
+  int vec[3];
+  float* dst;
+  long ld_dst;
+  long total;  // M * U
+  int U;       // units per row, all sources
+};
+
+__global__ __launch_bounds__(256) void ens_pack_rows_kernel(EnsPackParams p) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= p.total) return;
+  const long m = i / p.U;
+  int u = (int)(i - m * p.U);
+  int s = 0;
+  if (u >= p.units[0]) {
+    u -= p.units[0];
+    s = 1;
+    if (u >= p.units[1]) {
+      u -= p.units[1];
+      s = 2;
+    }
+  }
+  const float* src = p.src[s] + m * p.ld[s];
+  float* dst = p.dst + m * p.ld_dst + p.off[s];
+  if (p.vec[s])
+    reinterpret_cast<float4*>(dst)[u] = reinterpret_cast<const float4*>(src)[u];
+  else
+    dst[u] = src[u];
+}
+
 static bool fits_int(long v) { return v >= 0 && v <= 0x7fffffffL; }
 
 }  // namespace dv3
@@ -524,5 +565,43 @@ extern "C" int dv3_ens_disag_bwd(float* mu, const float* disag, const float* dre
   if (!fits_int(blocks)) return DV3_ERR_ARG;
   hipLaunchKernelGGL(ens_disag_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, mu, disag,
                      dreward, lddr, members, M, W, scale, use_log ? 1 : 0);
+  return (int)hipGetLastError();
+}
+
+static bool aligned16(const void* q) { return (reinterpret_cast<unsigned long long>(q) & 15ull) == 0; }
+
+extern "C" int dv3_ens_pack_rows(const float* src0, long ld0, int w0, const float* src1, long ld1, int w1,
+                                 const float* src2, long ld2, int w2, float* dst, long ld_dst, long M, void* stream) {
+  const float* src[3] = {src0, src1, src2};
+  const long ld[3] = {ld0, ld1, ld2};
+  const int w[3] = {w0, w1, w2};
+  if (M < 0 || w0 < 0 || w1 < 0 || w2 < 0) return DV3_ERR_ARG;
+  const long W = (long)w0 + w1 + w2;
+  if (!fits_int(W)) return DV3_ERR_ARG;
+  for (int i = 0; i < 3; ++i)
+    if (w[i] > 0 && (!src[i] || ld[i] < w[i])) return DV3_ERR_ARG;
+  if (W > 0 && (!dst || ld_dst < W)) return DV3_ERR_ARG;
+  if (M == 0 || W == 0) return 0;
+  EnsPackParams p{};
+  p.dst = dst;
+  p.ld_dst = ld_dst;
+  int off = 0, U = 0;
+  for (int i = 0; i < 3; ++i) {
+    p.src[i] = src[i];
+    p.ld[i] = ld[i];
+    p.off[i] = off;
+    p.vec[i] = (w[i] > 0 && w[i] % 4 == 0 && off % 4 == 0 && ld[i] % 4 == 0 && ld_dst % 4 == 0 && aligned16(src[i]) &&
+                aligned16(dst))
+                   ? 1
+                   : 0;
+    p.units[i] = p.vec[i] ? w[i] / 4 : w[i];
+    U += p.units[i];
+    off += w[i];
+  }
+  p.U = U;
+  p.total = M * (long)U;
+  const long blocks = (p.total + 255) / 256;
+  if (M > 0x7fffffffL || !fits_int(blocks)) return DV3_ERR_ARG;
+  hipLaunchKernelGGL(ens_pack_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
   return (int)hipGetLastError();
 }

@@ -2043,3 +2043,29 @@ def ens_disag_bwd(mu, disag, dreward, *, scale=1.0, log=True):
           _stream(), key="dv3_ens_disag_bwd" + (f"[{K}x{M}x{W}]" if PROFILE.by_shape else ""),
           nbytes=12.0 * K * M * W)
     return mu
+
+
+def ens_pack_rows(dst, *srcs):
+    """dst[:, off_i : off_i + w_i] = srcs[i] for up to three 2-D sources side by side (off_i: the running sum of their
+    widths; a source of width 0, or None, is absent) in ONE launch: the ensemble's input [stoch | deter | action] and
+    its target from row / column slices of larger buffers.  Row strides are free (>= the width); 4-byte alignment is
+    enough (16-byte vector stores where a source's address, strides and width allow)."""
+    if not 1 <= len(srcs) <= 3:
+        raise ValueError(f"ens_pack_rows: 1 to 3 sources, got {len(srcs)}")
+    M, W, ld_dst = _rows2d(dst, "dst")
+    args, total = [], 0
+    for i in range(3):
+        s = srcs[i] if i < len(srcs) else None
+        if s is None or (s.dim() == 2 and s.shape[1] == 0):
+            args += [0, 0, 0]
+            continue
+        r, c, ld = _rows2d(s, f"src{i}")
+        if r != M:
+            raise ValueError(f"ens_pack_rows: src{i} has {r} rows, dst has {M}")
+        args += [_ptr(s), ld, c]
+        total += c
+    if total != W:
+        raise ValueError(f"ens_pack_rows: the sources are {total} wide together, dst is {W}")
+    _call("dv3_ens_pack_rows", *args, _ptr(dst), ld_dst, M, _stream(),
+          key="dv3_ens_pack_rows" + (f"[{M}x{W}]" if PROFILE.by_shape else ""), nbytes=8.0 * M * W)
+    return dst

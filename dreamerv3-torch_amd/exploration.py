@@ -76,16 +76,14 @@ class Plan2Explore(nn.Module):
     # -- the fused path -----------------------------------------------------------------------------------------
     def _wants_fused(self) -> bool:
         cfg = self._config
-        return (bool(getattr(cfg, "expl_fused", True)) and bool(cfg.dyn_discrete) and cfg.disag_models >= 2
-                and cfg.disag_layers >= 1 and cfg.disag_units <= 2048)
+        return (bool(getattr(cfg, "expl_fused", True)) and cfg.disag_models >= 2 and cfg.disag_layers >= 1
+                and cfg.disag_units <= 2048)
 
     def fused_reason(self):
         """None when train_fwd_bwd / train_opt can run this configuration, else why not (then `train` is the path)."""
         cfg = self._config
         if not bool(getattr(cfg, "expl_fused", True)):
             return "expl_fused is off"
-        if not cfg.dyn_discrete:
-            return "continuous latents (dyn_discrete: 0)"
         if cfg.disag_models < 2 or cfg.disag_layers < 1 or cfg.disag_units > 2048:
             return "ensemble shape (needs >= 2 members, >= 1 layer, <= 2048 units)"
         if self._expl_opt.bucket.members < 2:
@@ -132,6 +130,8 @@ class Plan2Explore(nn.Module):
         if why is not None:
             raise NotImplementedError(f"Plan2Explore.train_fwd_bwd: {why}")
         cfg = self._config
+        if not cfg.dyn_discrete:
+            return self._regress_gauss(start, context, data)
         eng, _ = self._ensemble()
         stoch = start["stoch"]
         stoch = stoch.reshape(tuple(stoch.shape[:-2]) + (stoch.shape[-2] * stoch.shape[-1],))
@@ -155,6 +155,46 @@ class Plan2Explore(nn.Module):
         tg.copy_(target[:, off:])
         self._expl_opt.begin()
         self._loss = eng.regress_fwd_bwd(x.view(B * T, -1), tg.view(B * T, -1))
+
+    def _regress_gauss(self, start, context, data):
+        """train_regress for continuous latents (dyn_discrete: 0): stoch is [B, T, S] (nothing to flatten), the input
+        is [stoch | deter | action?] and every disag_target is well-formed (feat = [stoch | deter], S + De wide:
+        exploration.py:54-59).  Input and target are assembled by ops.ens_pack_rows, one launch each, with the rows in
+        TIME-major order (t * B + b): the posterior of WorldModel._train is a [B, T] view of time-major storage, so
+        its steps [0, T - off) and [off, T) are row ranges of one 2-D matrix.  The regression is a mean over the rows;
+        their order is free."""
+        from dv3hip import ops
+
+        cfg = self._config
+        eng, _ = self._ensemble()
+        off = cfg.disag_offset
+
+        def tm(v):  # [B, T, W] -> contiguous [T, B, W]; no copy for the world model's own time-major tensors
+            v = v.transpose(0, 1)
+            return v if v.is_contiguous() else v.contiguous()
+
+        stoch, deter = tm(start["stoch"]), tm(start["deter"])
+        Tall, B = deter.shape[0], deter.shape[1]
+        T = Tall - off
+        S, De = stoch.shape[-1], deter.shape[-1]
+        A = cfg.num_actions if cfg.disag_action_cond else 0
+        ws = eng.ws
+        rows = lambda v, lo, hi: v[lo:hi].reshape((hi - lo) * B, v.shape[-1])
+        act = None
+        if A:
+            act = data["action"]
+            act = act if isinstance(act, torch.Tensor) else torch.as_tensor(np.asarray(act))
+            act = ops.transpose01(act.to(stoch.device, torch.float32).contiguous(), ws.get("p2e.act_tm", (Tall, B, A)))
+        x = ws.get("p2e.x", (T * B, S + De + A))
+        ops.ens_pack_rows(x, rows(stoch, 0, T), rows(deter, 0, T), rows(act, 0, T) if A else None)
+        # (feat from the posterior, not context["feat"]: `context` caches what it computes lazily, and a replayed
+        # launch sequence must not depend on whether somebody has read it before)
+        parts = dict(embed=lambda: (tm(context["embed"]),), stoch=lambda: (stoch,), deter=lambda: (deter,),
+                     feat=lambda: (stoch, deter))[cfg.disag_target]()
+        tg = ws.get("p2e.target", (T * B, sum(p.shape[-1] for p in parts)))
+        ops.ens_pack_rows(tg, *[rows(p, off, Tall) for p in parts])
+        self._expl_opt.begin()
+        self._loss = eng.regress_fwd_bwd(x, tg)
 
     def train_behave(self, start, noise=None, allreduce=True):
         """The ensemble's clip + Adam step, then the exploration behaviour's forward / backward on the updated

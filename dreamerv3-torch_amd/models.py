@@ -827,17 +827,18 @@ class ImagBehavior(nn.Module):
         # the third kind of objective: the disagreement of a Plan2Explore ensemble, recognised by identity (an
         # EnsembleObjective, not a callable to probe) -- member-batched kernels forward and backward, no autograd
         ens = objective if isinstance(objective, EnsembleObjective) else None
-        if ens is not None and gauss:
-            raise NotImplementedError("the fused ensemble objective needs discrete latents (dyn_discrete > 0)")
         custom = ens is None and objective is not None and self.__dict__.get("_objective_kinds", {}).get(
             self._objective_key(objective)) is False
         r_logits = obj_out = obj_leaves = ens_x = None
         if ens is not None:
             F_ = SD + De
             ens_x = g("bh.ens_x", (HN, F_ + (A if ens.action_cond else 0)))
-            ens_x[:, :SD].copy_(fs), ens_x[:, SD:F_].copy_(fd)
-            if ens.action_cond:
-                ens_x[:, F_:].copy_(action.view(HN, A))
+            if gauss:  # [stoch | deter | action?] in one launch (the categorical route keeps its launch sequence)
+                ops.ens_pack_rows(ens_x, fs, fd, action.view(HN, A) if ens.action_cond else None)
+            else:
+                ens_x[:, :SD].copy_(fs), ens_x[:, SD:F_].copy_(fd)
+                if ens.action_cond:
+                    ens_x[:, F_:].copy_(action.view(HN, A))
             ens.engine.disag_fwd(ens_x, reward.view(HN, 1), keep=use_dyn and ens.action_cond)
             if ens.extr_scale:
                 _, r_logits, _ = reng.forward(fs, fd, idx=fidx, D=D)

@@ -540,6 +540,14 @@ int dv3_ens_disag_fwd(const float* h, long ldh, long strideH, const float* w, lo
 /* In place mu [K][M][W] -> d(sum_m dreward[m*lddr] reward[m]) / d pre_k (through std, mean, f and tanh). */
 int dv3_ens_disag_bwd(float* mu, const float* disag, const float* dreward, long lddr, int members, int M, int W,
                       float scale, int use_log, void* stream);
+/* Row packing of the ensemble's inputs: dst[m*ld_dst + off_i + c] = src_i[m*ld_i + c] for c < w_i, m < M, with
+ * off_0 = 0, off_1 = w0, off_2 = w0 + w1 (the shared input [stoch | deter | action] and the regression target, from
+ * slices of larger buffers, in ONE launch).  A source is absent when its w_i is 0 (its pointer is not read).
+ * ld_i >= w_i and ld_dst >= w0 + w1 + w2 in floats; the pointers need 4-byte alignment only: a source moves as
+ * 16-byte vectors when its base, row strides, width and destination offset allow it, as dwords otherwise.  Sources
+ * must not overlap dst.  M == 0 or no columns: nothing is launched. */
+int dv3_ens_pack_rows(const float* src0, long ld0, int w0, const float* src1, long ld1, int w1, const float* src2,
+                      long ld2, int w2, float* dst, long ld_dst, long M, void* stream);
 
 /* ---- compute-unit partitioned streams (csrc/streams.hip) --------------------------------------------------------
  * The MI355X-native counterpart of nothing in the reference (its update is one stream of ATen launches,

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Device time of one Plan2Explore exploration update (ensemble regression + Adam, exploration behaviour on the
-disagreement reward) at cfg 2 with the stock exploration settings of configs.yaml, MI355X only:
+disagreement reward) at cfg 2 -- categorical latents (`cfg2`) or continuous ones (`cfg2_gauss`, dyn_discrete: 0) --
+with the stock exploration settings of configs.yaml, MI355X only:
 
   * autograd route  -- exploration.Plan2Explore.train (expl_fused False: the parent path), eager;
   * fused           -- train_fwd_bwd + train_opt on the member-batched ensemble kernels, eager and as a hipGraph replay;
@@ -13,7 +14,7 @@ intervals around whole updates.  The EAGER figures therefore include the host's 
 small launches is bounded by the host, not by the device); the replay figure is device time and covers the fused route
 only (the autograd route cannot be captured).
 
-    python tools/expl_bench.py [cfg2] [--json out.json] [--no-replay]
+    python tools/expl_bench.py [cfg2 | cfg2_gauss] [--json out.json] [--no-replay]
 """
 import json
 import os
@@ -26,7 +27,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from tests import helpers as Hh  # noqa: E402
-from tests.golden import common  # noqa: E402
+from tests.golden import common, gauss_common  # noqa: E402
 
 PEAK_TFLOPS = 157.3  # fp32 matrix peak (README)
 
@@ -49,7 +50,9 @@ def main():
     out_json = sys.argv[sys.argv.index("--json") + 1] if "--json" in sys.argv else None
     args = [a for a in sys.argv[1:] if not a.startswith("--") and a != out_json]
     name = args[0] if args else "cfg2"
-    cfg, wm, _ = Hh.build_models(name)
+    # (continuous latents: `stoch` wide states and 2 * stoch wide stat layers, gauss_common's weight table)
+    weights = None if common.SHAPES[name]["discrete"] else gauss_common.make_weights(name)
+    cfg, wm, _ = Hh.build_models(name, weights=weights)
     cfg.expl_behavior = "plan2explore"
     torch.manual_seed(0)
     p2e = exploration.Plan2Explore(cfg, wm, lambda f, st, a: wm.heads["reward"](f).mean()).cuda()
@@ -73,7 +76,7 @@ def main():
     for _ in range(7):  # alternating
         t_a.append(event_ms(autograd_update))
         t_f.append(event_ms(fused_update))
-    res = dict(config=name, disag_models=cfg.disag_models, disag_layers=cfg.disag_layers, disag_units=cfg.disag_units,
+    res = dict(config=name, dyn_discrete=cfg.dyn_discrete, disag_target=cfg.disag_target, disag_models=cfg.disag_models, disag_layers=cfg.disag_layers, disag_units=cfg.disag_units,
                autograd_eager_ms=float(np.median(t_a)), fused_eager_ms=float(np.median(t_f)),
                autograd_eager_all_ms=t_a, fused_eager_all_ms=t_f)
     ops.PROFILE.by_shape = False
