@@ -1341,13 +1341,21 @@ extern "C" int dv3_pack_conv_weight(const float* w, float* wp, int Co, int Ci, i
 // (tap offset, zero for padding taps) and both operands sit k-contiguous in LDS (stride 40 floats), so an MFMA
 // fragment for four k-steps is one ds_read_b128 -- against the k-major image of the 32x32x2 tile engine above that is
 // a quarter of the LDS instructions and no transposing ds_write_b32.  4 waves (2 x 2), v_mfma_f32_16x16x4_f32,
-// double-buffered LDS, global loads of tile t+1 in flight during the MFMAs of tile t; padding is zeroed when the
-// tile is written to LDS (not when it is loaded: that would make the wave wait for its own prefetch).
+// double-buffered LDS, one barrier per K-tile; padding is zeroed when the tile is written to LDS (not when it is
+// loaded: that would make the wave wait for its own prefetch).  The K loop is the software-pipelined one of
+// gemm_l16_kernel (VAR bit 0; two fragment sets):
+//   reads (t, 1) | MFMAs (t, 0) g 0-1 | ds_write t+1 -> cur^1 | global loads t+2 | MFMAs (t, 0) g 2-3 | barrier |
+//   reads (t+1, 0) | MFMAs (t, 1)
+// with the same ascending (t, kk, g) order per accumulator as the serial loop (VAR bit 0 clear; development library,
+// DV3_L16_LOOP=0).  Epilogue (VAR bit 1): the output pixel of a row is decoded once per row (shifts when H and W are
+// powers of two, one division pair per row otherwise) instead of once per element, the reads of y the accumulate
+// path needs are issued per row block ahead of the stores, and the stores go out together (serial form:
+// DV3_L16_EPI=0, development library).
 // ------------------------------------------------------------------------------------------------
 // TR = false: conv_s2 (rows = output pixels, K = 16 Ci, taps (ky, kx), input at (2oy-1+ky, 2ox-1+kx)).
 // TR = true : convT_s2, one parity class (py, px) = blockIdx.y per grid row (rows = INPUT pixels (y, x), K = 4 Ci, taps
 //             (a, b), input at (y+py-a, x+px-b), weights wp[cls][Co][4 Ci], output pixel (2y+py, 2x+px); + bias, + out_add).
-template <int BM, int BN, bool TR>
+template <int BM, int BN, bool TR, int VAR = 3>
 __global__ __launch_bounds__(256) void conv_s2_l16_kernel(ConvParams p) {
   constexpr int BK = 32, LD = 40;
   constexpr int WM = 2, WN = 2;                // waves: 2 x 2
@@ -1431,9 +1439,47 @@ __global__ __launch_bounds__(256) void conv_s2_l16_kernel(ConvParams p) {
   const int nk = K / BK;
   gload(0);
   lstore(0);
+  if constexpr (VAR & 1) {
+    if (nk > 1) gload(BK);
+  }
   __syncthreads();
   const int aoff = (wm * (16 * TM) + i) * LD + 4 * q;
   const int boff = (wn * (16 * TN) + i) * LD + 4 * q;
+  if constexpr (VAR & 1) {
+    f32x4 af[2][TM], bf[2][TN];
+    auto fread = [&](int s, int buf, int kk) {
+#pragma unroll
+      for (int a = 0; a < TM; ++a) af[s][a] = *reinterpret_cast<const f32x4*>(&As[buf][aoff + 16 * a * LD + 16 * kk]);
+#pragma unroll
+      for (int b = 0; b < TN; ++b) bf[s][b] = *reinterpret_cast<const f32x4*>(&Bs[buf][boff + 16 * b * LD + 16 * kk]);
+    };
+    auto mma = [&](int s, int g0, int g1) {
+#pragma unroll
+      for (int g = g0; g < g1; ++g)
+#pragma unroll
+        for (int a = 0; a < TM; ++a)
+#pragma unroll
+          for (int b = 0; b < TN; ++b)
+            acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[s][a][g], bf[s][b][g], acc[a][b], 0, 0, 0);
+    };
+    fread(0, 0, 0);
+    // K-tiles 0 .. nk-2: tile t+1 is already in the staging registers (prologue / the loads issued during tile t-1)
+    for (int t = 0; t + 1 < nk; ++t) {
+      const int cur = t & 1;
+      fread(1, cur, 1);
+      mma(0, 0, 2);
+      lstore(cur ^ 1);  // mid-chunk: the writes land while the second half multiplies
+      if (t + 2 < nk) gload((t + 2) * BK);
+      mma(0, 2, 4);
+      __syncthreads();
+      fread(0, cur ^ 1, 0);
+      mma(1, 0, 4);
+    }
+    // drain: the last K-tile has nothing to stage and needs no barrier
+    fread(1, (nk - 1) & 1, 1);
+    mma(0, 0, 4);
+    mma(1, 0, 4);
+  } else
   for (int t = 0; t < nk; ++t) {
     const int cur = t & 1;
     if (t + 1 < nk) gload((t + 1) * BK);
@@ -1454,6 +1500,65 @@ __global__ __launch_bounds__(256) void conv_s2_l16_kernel(ConvParams p) {
     }
     if (t + 1 < nk) lstore(cur ^ 1);
     __syncthreads();
+  }
+  if constexpr (VAR & 2) {
+    // a lane's TM x TN x 4 outputs are distinct addresses: the reads of y need not wait for the lane's own stores
+    float add[TN];
+    bool colok[TN];
+#pragma unroll
+    for (int b = 0; b < TN; ++b) {
+      const int col = n0 + wn * (16 * TN) + 16 * b + i;
+      colok[b] = col < p.Co;
+      add[b] = TR ? ((p.bias && colok[b]) ? p.bias[col] : 0.f) + p.out_add : 0.f;
+    }
+    float* const ycol = p.y + n0 + wn * (16 * TN) + i;  // + 16 b per column block
+    const bool pow2 = (p.W & (p.W - 1)) == 0 && (p.H & (p.H - 1)) == 0;  // uniform
+    const int sw = 31 - __builtin_clz(p.W), sh = 31 - __builtin_clz(p.H);
+    // element offset of row `row` in y (without the column); row < M
+    auto rowoff = [&](long row) -> long {
+      if constexpr (!TR) return row * p.Co;
+      long img;
+      int y2, x2;
+      if (pow2) {
+        x2 = (int)(row & (p.W - 1));
+        const long t = row >> sw;
+        y2 = (int)(t & (p.H - 1));
+        img = t >> sh;
+      } else {
+        const long t = row / p.W;
+        x2 = (int)(row - t * p.W);
+        img = t / p.H;
+        y2 = (int)(t - img * p.H);
+      }
+      return ((img * (2 * p.H) + 2 * y2 + py) * (2L * p.W) + 2 * x2 + px) * p.Co;
+    };
+    long off[2][4];  // < 0: row past the edge
+    float cv[2][TN][4];
+    auto prep = [&](int s, int a) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const long row = m0 + wm * (16 * TM) + 16 * a + 4 * q + r;
+        off[s][r] = row < M ? rowoff(row) : -1;
+        if (p.accumulate) {
+#pragma unroll
+          for (int b = 0; b < TN; ++b) cv[s][b][r] = (colok[b] && off[s][r] >= 0) ? ycol[off[s][r] + 16 * b] : 0.f;
+        }
+      }
+    };
+    prep(0, 0);
+#pragma unroll
+    for (int a = 0; a < TM; ++a) {
+      if (a + 1 < TM) prep((a + 1) & 1, a + 1);
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int b = 0; b < TN; ++b) {
+          float v = acc[a][b][r] + add[b];
+          if (p.accumulate) v += cv[a & 1][b][r];
+          if (colok[b] && off[a & 1][r] >= 0) ycol[off[a & 1][r] + 16 * b] = v;
+        }
+    }
+    return;
   }
 #pragma unroll
   for (int a = 0; a < TM; ++a)
@@ -1646,6 +1751,22 @@ extern "C" int dv3_im2col_s2(const float* x, float* cols, int Nimg, int H, int W
   return (int)hipGetLastError();
 }
 
+// conv_s2_l16_kernel launch; the development library can take the serial K loop and / or the serial epilogue
+// (DV3_L16_LOOP=0, DV3_L16_EPI=0: A/B of each mechanism on its own)
+#ifdef DV3_DEV_SWITCHES
+#define DV3_CONV_L16_LAUNCH(BM_, BN_, TR_)                                                                   \
+  do {                                                                                                       \
+    static const int var_ = (DV3_ENV_INT("DV3_L16_LOOP", 1) ? 1 : 0) | (DV3_ENV_INT("DV3_L16_EPI", 1) ? 2 : 0); \
+    if (var_ == 0) hipLaunchKernelGGL((conv_s2_l16_kernel<BM_, BN_, TR_, 0>), grid, dim3(256), 0, s, p);      \
+    else if (var_ == 1) hipLaunchKernelGGL((conv_s2_l16_kernel<BM_, BN_, TR_, 1>), grid, dim3(256), 0, s, p); \
+    else if (var_ == 2) hipLaunchKernelGGL((conv_s2_l16_kernel<BM_, BN_, TR_, 2>), grid, dim3(256), 0, s, p); \
+    else hipLaunchKernelGGL((conv_s2_l16_kernel<BM_, BN_, TR_, 3>), grid, dim3(256), 0, s, p);               \
+  } while (0)
+#else
+#define DV3_CONV_L16_LAUNCH(BM_, BN_, TR_) \
+  hipLaunchKernelGGL((conv_s2_l16_kernel<BM_, BN_, TR_, 3>), grid, dim3(256), 0, s, p)
+#endif
+
 extern "C" int dv3_conv_s2_fwd(const float* x, const float* w_packed, float* y, int Nimg, int H, int W, int Ci, int Co,
                                int accumulate, void* stream) {
   if (Nimg <= 0) return 0;
@@ -1676,11 +1797,11 @@ extern "C" int dv3_conv_s2_fwd(const float* x, const float* w_packed, float* y, 
     p.tiles_m = (int)((M + bm - 1) / bm);
     p.tiles_n = (Co + bn - 1) / bn;
     const dim3 grid((unsigned)(p.tiles_m * p.tiles_n));
-    if (bn == 128 && big) hipLaunchKernelGGL((conv_s2_l16_kernel<128, 128, false>), grid, dim3(256), 0, s, p);
-    else if (bn == 128) hipLaunchKernelGGL((conv_s2_l16_kernel<64, 128, false>), grid, dim3(256), 0, s, p);
-    else if (bn == 96 && big) hipLaunchKernelGGL((conv_s2_l16_kernel<128, 96, false>), grid, dim3(256), 0, s, p);
-    else if (bn == 96) hipLaunchKernelGGL((conv_s2_l16_kernel<64, 96, false>), grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((conv_s2_l16_kernel<64, 64, false>), grid, dim3(256), 0, s, p);
+    if (bn == 128 && big) DV3_CONV_L16_LAUNCH(128, 128, false);
+    else if (bn == 128) DV3_CONV_L16_LAUNCH(64, 128, false);
+    else if (bn == 96 && big) DV3_CONV_L16_LAUNCH(128, 96, false);
+    else if (bn == 96) DV3_CONV_L16_LAUNCH(64, 96, false);
+    else DV3_CONV_L16_LAUNCH(64, 64, false);
     return (int)hipGetLastError();
   }
   static const int env_direct = DV3_ENV_INT("DV3_CONV_DIRECT", 64);
@@ -1742,12 +1863,12 @@ extern "C" int dv3_convT_s2_fwd(const float* x, const float* w_packed, const flo
     p.tiles_m = (int)((M + bm - 1) / bm);
     p.tiles_n = (Co + bn - 1) / bn;
     const dim3 grid(convT_grid((long)p.tiles_m * p.tiles_n));
-    if (bn == 128 && big) hipLaunchKernelGGL((conv_s2_l16_kernel<128, 128, true>), grid, dim3(256), 0, s, p);
-    else if (bn == 128) hipLaunchKernelGGL((conv_s2_l16_kernel<64, 128, true>), grid, dim3(256), 0, s, p);
-    else if (bn == 96 && big) hipLaunchKernelGGL((conv_s2_l16_kernel<128, 96, true>), grid, dim3(256), 0, s, p);
-    else if (bn == 96) hipLaunchKernelGGL((conv_s2_l16_kernel<64, 96, true>), grid, dim3(256), 0, s, p);
-    else if (bn == 64) hipLaunchKernelGGL((conv_s2_l16_kernel<64, 64, true>), grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((conv_s2_l16_kernel<128, 32, true>), grid, dim3(256), 0, s, p);
+    if (bn == 128 && big) DV3_CONV_L16_LAUNCH(128, 128, true);
+    else if (bn == 128) DV3_CONV_L16_LAUNCH(64, 128, true);
+    else if (bn == 96 && big) DV3_CONV_L16_LAUNCH(128, 96, true);
+    else if (bn == 96) DV3_CONV_L16_LAUNCH(64, 96, true);
+    else if (bn == 64) DV3_CONV_L16_LAUNCH(64, 64, true);
+    else DV3_CONV_L16_LAUNCH(128, 32, true);
     return (int)hipGetLastError();
   }
   static const int env_direct = DV3_ENV_INT("DV3_CONVT_DIRECT", 128);

@@ -704,13 +704,25 @@ static void launch_direct(const GemmParams& p, hipStream_t s) {
 // Row stride 40 floats: the 16 lanes a ds_read_b128 serves together (0-3, 12-15, 20-27 | ...) then cover all 64
 // banks exactly once (i*40 + 4q mod 64 is a permutation of the 16 four-bank windows), and the 8 lanes of a
 // ds_write_b128 group write 128 contiguous bytes.  One workgroup = 4 waves (2 x 2) = one BM x BN tile, BK = 32,
-// double-buffered: global loads of K-tile t+1 are issued before the MFMAs of tile t, one barrier per K-tile.
+// double-buffered, one barrier per K-tile.  The K loop is software-pipelined inside the wave (VAR bit 0): two fragment
+// sets, so that the ds_read_b128 of the next 16-k chunk, the ds_write_b128 of the next K-tile and the global loads of
+// the tile after it are all issued with MFMAs of the same wave behind them:
+//   reads (t, 1) | MFMAs (t, 0) g 0-1 | ds_write t+1 -> cur^1 | global loads t+2 | MFMAs (t, 0) g 2-3 | barrier |
+//   reads (t+1, 0) | MFMAs (t, 1)
+// (the barrier of t-1 came after every read of cur^1; every read of cur is complete at the barrier of t).  Each
+// accumulator still receives its MFMAs in ascending (t, kk, g): bit-equal to the serial loop (VAR bit 0 clear: read,
+// wait, multiply per chunk), which the 128 x 128 tile keeps (launch_l16) and the development library can select for
+// every tile (DV3_L16_LOOP=0).
+// Epilogue (VAR bit 1): per row block a, every C element the accumulate path needs is loaded (those of block a + 1
+// before the stores of block a) and the stores are issued together; the serial form (DV3_L16_EPI=0, development
+// library) reads, adds and stores one element at a time, each waiting for the store before it.
 // Tile shapes 32x64 / 64x64 / 64x96 / 128x128, picked by output size (launch_l16 / pick_tile; measurements in
 // dv3hip/ops.py pick_gemm_tile).  Tile order: xcd_tile (each XCD owns a block of tiles chosen by operand bytes).
 // Requires K % 32 == 0, K1 % 32 == 0, lda/lda2/ldb % 4 == 0, 16-byte aligned operands (l16_ok).
 // ------------------------------------------------------------------------------------------------
-template <int BM, int BN, int PF, int EPI = 0>
+template <int BM, int BN, int PF, int EPI = 0, int VAR = 3>
 __global__ __launch_bounds__(256) void gemm_l16_kernel(GemmParams p) {
+  static_assert(PF == 1 || !(VAR & 1), "the pipelined loop has one staging register set");
   constexpr int BK = 32, LD = 40;
   constexpr int TMW = BM / 32, TNW = BN / 32;  // 16 x 16 blocks per wave (wave tile = BM/2 x BN/2)
   constexpr int NA = BM * (BK / 4) / 256, NB = BN * (BK / 4) / 256;
@@ -772,9 +784,47 @@ __global__ __launch_bounds__(256) void gemm_l16_kernel(GemmParams p) {
 #pragma unroll
   for (int u = 1; u < PF; ++u)
     if (u < nk) gload(ra[u], rb[u], u * BK);
+  if constexpr (VAR & 1) {
+    if (nk > 1) gload(ra[0], rb[0], BK);
+  }
   __syncthreads();
   const int aoff = (wm * (BM / 2) + i) * LD + 4 * q;
   const int boff = (wn * (BN / 2) + i) * LD + 4 * q;
+  if constexpr (VAR & 1) {
+    f32x4 af[2][TMW], bf[2][TNW];
+    auto fread = [&](int s, int buf, int kk) {
+#pragma unroll
+      for (int a = 0; a < TMW; ++a) af[s][a] = *reinterpret_cast<const f32x4*>(&As[buf][aoff + 16 * a * LD + 16 * kk]);
+#pragma unroll
+      for (int b = 0; b < TNW; ++b) bf[s][b] = *reinterpret_cast<const f32x4*>(&Bs[buf][boff + 16 * b * LD + 16 * kk]);
+    };
+    auto mma = [&](int s, int g0, int g1) {
+#pragma unroll
+      for (int g = g0; g < g1; ++g)
+#pragma unroll
+        for (int a = 0; a < TMW; ++a)
+#pragma unroll
+          for (int b = 0; b < TNW; ++b)
+            acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[s][a][g], bf[s][b][g], acc[a][b], 0, 0, 0);
+    };
+    fread(0, 0, 0);
+    // K-tiles 0 .. nk-2: tile t+1 is already in the staging registers (prologue above / step 4 of tile t-1)
+    for (int t = 0; t + 1 < nk; ++t) {
+      const int cur = t & 1;
+      fread(1, cur, 1);
+      mma(0, 0, 2);
+      lstore(ra[0], rb[0], cur ^ 1);  // mid-chunk: the writes land while the second half multiplies
+      if (t + 2 < nk) gload(ra[0], rb[0], (t + 2) * BK);
+      mma(0, 2, 4);
+      __syncthreads();
+      fread(0, cur ^ 1, 0);
+      mma(1, 0, 4);
+    }
+    // drain: the last K-tile (the only one when nk == 1) has nothing to stage and needs no barrier
+    fread(1, (nk - 1) & 1, 1);
+    mma(0, 0, 4);
+    mma(1, 0, 4);
+  } else
   for (int t0 = 0; t0 < nk; t0 += PF)
 #pragma unroll
   for (int u = 0; u < PF; ++u) {
@@ -902,6 +952,49 @@ __global__ __launch_bounds__(256) void gemm_l16_kernel(GemmParams p) {
     return;
   }
   // accumulator register r of block (a, b): row 16 a + 4 q + r, column 16 b + i
+  if constexpr (VAR & 2) {
+    // a lane's TMW x TNW x 4 outputs are distinct addresses: the reads of C need not wait for the lane's own stores
+    float bv[TNW];
+    float* cbase[TNW];  // nullptr: column past the edge
+    long ldo[TNW];
+    bool accf[TNW];
+#pragma unroll
+    for (int b = 0; b < TNW; ++b) {
+      const int col = n0 + wn * (BN / 2) + 16 * b + i;
+      const bool ok = col < p.N;
+      const bool second = p.C2 && col >= p.nsplit;
+      bv[b] = (ok && p.bias) ? p.bias[col] : 0.f;
+      cbase[b] = !ok ? nullptr : second ? p.C2 + (col - p.nsplit) : p.C + col;
+      ldo[b] = second ? p.ldc2 : p.ldc;
+      accf[b] = ok && (second ? p.accumulate2 : p.accumulate);
+    }
+    float cv[2][TNW][4];
+    auto cload = [&](int s, int a) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = m0 + wm * (BM / 2) + 16 * a + 4 * q + r;
+#pragma unroll
+        for (int b = 0; b < TNW; ++b) cv[s][b][r] = (accf[b] && row < p.M) ? cbase[b][(long)row * ldo[b]] : 0.f;
+      }
+    };
+    const bool any_acc = p.accumulate || (p.C2 && p.accumulate2);  // uniform
+    if (any_acc) cload(0, 0);
+#pragma unroll
+    for (int a = 0; a < TMW; ++a) {
+      if (any_acc && a + 1 < TMW) cload((a + 1) & 1, a + 1);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = m0 + wm * (BM / 2) + 16 * a + 4 * q + r;
+#pragma unroll
+        for (int b = 0; b < TNW; ++b) {
+          float v = acc[a][b][r] + bv[b];
+          if (accf[b]) v += cv[a & 1][b][r];
+          if (cbase[b] && row < p.M) cbase[b][(long)row * ldo[b]] = v;
+        }
+      }
+    }
+    return;
+  }
 #pragma unroll
   for (int a = 0; a < TMW; ++a)
 #pragma unroll
@@ -932,7 +1025,15 @@ static void launch_l16_sample(const GemmParams& p0, hipStream_t s) {
   p.tiles_m = (p.M + 31) / 32;
   p.tiles_n = (p.N + 63) / 64;
   pick_xcd_grid(p);
-  hipLaunchKernelGGL((gemm_l16_kernel<32, 64, 1, 1>), dim3(p.tiles_m * p.tiles_n), dim3(256), 0, s, p);
+  const dim3 grid(p.tiles_m * p.tiles_n), block(256);
+#ifdef DV3_DEV_SWITCHES
+  static const int loop = DV3_ENV_INT("DV3_L16_LOOP", 1);
+  if (!loop) {
+    hipLaunchKernelGGL((gemm_l16_kernel<32, 64, 1, 1, 2>), grid, block, 0, s, p);
+    return;
+  }
+#endif
+  hipLaunchKernelGGL((gemm_l16_kernel<32, 64, 1, 1>), grid, block, 0, s, p);
 }
 
 static bool l16_ok(const GemmParams& p, int transA, int transB) {
@@ -959,18 +1060,31 @@ static void launch_l16(const GemmParams& p0, int force, hipStream_t s) {
   p.tiles_n = (p.N + bn - 1) / bn;
   pick_xcd_grid(p);
   const dim3 grid(p.tiles_m * p.tiles_n), block(256);
-  static const int pf = DV3_ENV_INT("DV3_L16_PF", 1);
-#define DV3_L16_LAUNCH(PFV)                                                                     \
-  do {                                                                                          \
-    if (sel == 1) hipLaunchKernelGGL((gemm_l16_kernel<64, 96, PFV>), grid, block, 0, s, p);      \
-    else if (sel == 2) hipLaunchKernelGGL((gemm_l16_kernel<64, 64, PFV>), grid, block, 0, s, p); \
-    else if (sel == 4) hipLaunchKernelGGL((gemm_l16_kernel<128, 128, PFV>), grid, block, 0, s, p); \
-    else if (sel == 5) hipLaunchKernelGGL((gemm_l16_kernel<128, 64, PFV>), grid, block, 0, s, p); \
-    else if (sel == 6) hipLaunchKernelGGL((gemm_l16_kernel<64, 128, PFV>), grid, block, 0, s, p); \
-    else hipLaunchKernelGGL((gemm_l16_kernel<32, 64, PFV>), grid, block, 0, s, p);               \
+#define DV3_L16_LAUNCH(PFV, VARV, VAR128)                                                                  \
+  do {                                                                                                     \
+    if (sel == 1) hipLaunchKernelGGL((gemm_l16_kernel<64, 96, PFV, 0, VARV>), grid, block, 0, s, p);         \
+    else if (sel == 2) hipLaunchKernelGGL((gemm_l16_kernel<64, 64, PFV, 0, VARV>), grid, block, 0, s, p);    \
+    else if (sel == 4) hipLaunchKernelGGL((gemm_l16_kernel<128, 128, PFV, 0, VAR128>), grid, block, 0, s, p); \
+    else if (sel == 5) hipLaunchKernelGGL((gemm_l16_kernel<128, 64, PFV, 0, VARV>), grid, block, 0, s, p);   \
+    else if (sel == 6) hipLaunchKernelGGL((gemm_l16_kernel<64, 128, PFV, 0, VARV>), grid, block, 0, s, p);   \
+    else hipLaunchKernelGGL((gemm_l16_kernel<32, 64, PFV, 0, VARV>), grid, block, 0, s, p);                 \
   } while (0)
-  if (pf == 2) DV3_L16_LAUNCH(2);
-  else DV3_L16_LAUNCH(1);
+#ifdef DV3_DEV_SWITCHES
+  // A/B of the loop and of the epilogue, each on its own (the serial loop also keeps the prefetch-distance switch).
+  // DV3_L16_LOOP: 0 serial on every tile, 1 pipelined on every tile, unset: as shipped.
+  static const int pf = DV3_ENV_INT("DV3_L16_PF", 1);
+  static const int loop = DV3_ENV_INT("DV3_L16_LOOP", -1), epi = DV3_ENV_INT("DV3_L16_EPI", 1);
+  if (!loop && pf == 2 && epi) { DV3_L16_LAUNCH(2, 2, 2); return; }
+  if (!loop && pf == 2) { DV3_L16_LAUNCH(2, 0, 0); return; }
+  if (!loop && epi) { DV3_L16_LAUNCH(1, 2, 2); return; }
+  if (!loop) { DV3_L16_LAUNCH(1, 0, 0); return; }
+  if (loop == 1 && epi) { DV3_L16_LAUNCH(1, 3, 3); return; }
+  if (loop == 1) { DV3_L16_LAUNCH(1, 1, 1); return; }
+  if (!epi) { DV3_L16_LAUNCH(1, 1, 0); return; }
+#endif
+  // the 128 x 128 tile keeps the serial loop: where it is the tile of choice (two workgroups per CU, in step) the
+  // pipelined loop measured no faster
+  DV3_L16_LAUNCH(1, 3, 2);
 #undef DV3_L16_LAUNCH
 }
 

@@ -230,12 +230,15 @@ def pick_gemm_tile(M: int, N: int, wgrad: bool = False, K: int = 0) -> int:
 #   1024 x 4096 x 1536 (decoder Linear)       128x128 202 / 64x64 236     14336 x 255 x 512 (head out)     128x128 76.7 / 64x64 82.7
 #   1024 x 1024 x 1536 | 4096 (rollout dgrad, encoder Linear dgrad)  64x64 62.3 | 157 / 32x64 65.2 | 164
 #   14336 x 512 x 512 (head layers)           64x64 146.7 / 128x128 150.6     (r04 sweep: profiles/r04_gemm_lane_sweep.txt)
+#   with the software-pipelined K loop of the smaller tiles (the 128x128 tile keeps the serial loop):
+#   15360 x 512 x 512 (head layers)  64x64 138.2 / 128x128 145.3     14336 x 255 x 512 (head out)  64x64 67.1 / 128x128 74.0
+#   (profiles/r05_l16_lane_ab.txt)
 # All of these tiles run the same K loop (32-wide K tiles, v_mfma_f32_16x16x4_f32 in ascending k): switching among them
 # changes no bit of the result (tests/test_kernels_gpu.py::test_l16_tiles_agree_bit_for_bit), so the lanes schedule still
 # computes exactly what the serial update computes.
 LANE_STREAMS = {}  # stream handle -> compute units of its queue
 _LANE_TILES = {(1024, 1536): 12, (2048, 3072): 16, (2048, 1024): 16, (15360, 255): 15, (14336, 1024): 13,
-               (1024, 4096): 15, (14336, 255): 15, (1024, 1024): 13, (14336, 512): 13,
+               (1024, 4096): 15, (14336, 255): 13, (1024, 1024): 13, (14336, 512): 13, (15360, 512): 13,
                (2048, 512): 13, (28672, 512): 13, (28672, 255): 13}  # (cfg 3: profiles/r04_gemm_lane_sweep_cfg3.txt)
 
 

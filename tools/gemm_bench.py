@@ -52,6 +52,7 @@ SHAPES = [
 
 
 ZEROS = False
+ACC = False  # --accumulate: C += ... for every shape (the reverse rollout's and the heads' data gradients)
 LANE = None  # --lane: replay on the 128-CU side lane (engine.Lanes) -- what a kernel sees in the pipelined update
 
 
@@ -64,7 +65,7 @@ def bench(M, N, K, tA, tB, tile, reps):
         A.zero_()
         B.zero_()
     C = torch.zeros(M, N, device=dev)
-    acc = bool(tA)
+    acc = bool(tA) or ACC
     fn = lambda: ops.gemm(A, B, C, transA=bool(tA), transB=bool(tB), tile=tile, accumulate=acc)
     for _ in range(3):
         fn()
@@ -95,13 +96,15 @@ def main():
     ap.add_argument("--only", default="", help="substring of the note column")
     ap.add_argument("--zeros", action="store_true", help="zero-filled operands (clock / power check)")
     ap.add_argument("--lane", action="store_true", help="replay on the 128-CU side lane instead of the whole chip")
+    ap.add_argument("--accumulate", action="store_true", help="C += ... (the epilogue reads C) for every shape")
     ap.add_argument("--shapes", default="", help='"M,N,K,tA,tB;..." instead of the built-in list')
     args = ap.parse_args()
     shapes = SHAPES
     if args.shapes:
         shapes = [tuple(int(x) for x in sh.split(",")) + ("",) for sh in args.shapes.split(";") if sh]
-    global ZEROS, LANE
+    global ZEROS, LANE, ACC
     ZEROS = args.zeros
+    ACC = args.accumulate
     if args.lane:
         from dv3hip import engine
 

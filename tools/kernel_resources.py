@@ -38,8 +38,8 @@ def main():
             dem = re.sub(r"\(.*", "", dem.strip()).replace("void ", "")
             if filt in dem:
                 vg, ag = int(cur.get("vgpr_count", 0)), int(cur.get("agpr_count", 0))
-                tot = -(-(vg + ag) // 8) * 8 if ag else vg  # unified file: arch VGPRs rounded up, then AGPRs
-                print(f"{dem[:78]:78s} vgpr {vg:4d} agpr {ag:4d} lds {int(cur.get('group_segment_fixed_size', 0)):6d} "
+                tot = -(-vg // 8) * 8  # gfx90a+: .vgpr_count is the wave's whole unified allocation, AGPRs included
+                print(f"{dem[:78]:78s} regs {vg:4d} (agpr {ag:4d}) lds {int(cur.get('group_segment_fixed_size', 0)):6d} "
                       f"scratch {cur.get('private_segment_fixed_size'):>4} spill {cur.get('vgpr_spill_count')} "
                       f"waves/SIMD<= {min(8, 512 // max(tot, 1))}")
             cur = {}
