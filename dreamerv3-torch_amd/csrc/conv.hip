@@ -15,6 +15,7 @@
 #include <stdlib.h>
 
 #include "mfma_gemm.h"
+#include "l16_tile.h"
 #include "dv3_common.h"
 
 namespace dv3 {
@@ -1335,39 +1336,27 @@ extern "C" int dv3_pack_conv_weight(const float* w, float* wp, int Co, int Ci, i
 }
 
 // ------------------------------------------------------------------------------------------------
-// conv_s2 as an implicit GEMM on the k-contiguous LDS tile scheme of gemm_l16_kernel (gemm.hip): M = output pixels,
-// N = Co, K = (ky, kx, ci).  With Ci % 32 == 0 a 32-wide K-tile is 32 consecutive channels of ONE tap, i.e. 128
-// contiguous bytes of the NHWC input per output pixel: the A staging is the dense loader with a per-tile row pointer
-// (tap offset, zero for padding taps) and both operands sit k-contiguous in LDS (stride 40 floats), so an MFMA
-// fragment for four k-steps is one ds_read_b128 -- against the k-major image of the 32x32x2 tile engine above that is
-// a quarter of the LDS instructions and no transposing ds_write_b32.  4 waves (2 x 2), v_mfma_f32_16x16x4_f32,
-// double-buffered LDS, one barrier per K-tile; padding is zeroed when the tile is written to LDS (not when it is
-// loaded: that would make the wave wait for its own prefetch).  The K loop is the software-pipelined one of
-// gemm_l16_kernel (VAR bit 0; two fragment sets):
-//   reads (t, 1) | MFMAs (t, 0) g 0-1 | ds_write t+1 -> cur^1 | global loads t+2 | MFMAs (t, 0) g 2-3 | barrier |
-//   reads (t+1, 0) | MFMAs (t, 1)
-// with the same ascending (t, kk, g) order per accumulator as the serial loop (VAR bit 0 clear; development library,
-// DV3_L16_LOOP=0).  Epilogue (VAR bit 1): the output pixel of a row is decoded once per row (shifts when H and W are
-// powers of two, one division pair per row otherwise) instead of once per element, the reads of y the accumulate
-// path needs are issued per row block ahead of the stores, and the stores go out together (serial form:
-// DV3_L16_EPI=0, development library).
+// conv_s2 as an implicit GEMM on the k-contiguous LDS tile engine of l16_tile.h (scheme, K loop and accumulator map
+// are described there): M = output pixels, N = Co, K = (ky, kx, ci).  With Ci % 32 == 0 a 32-wide K-tile is 32
+// consecutive channels of ONE tap, i.e. 128 contiguous bytes of the NHWC input per output pixel: the A staging is the
+// dense loader with a per-tile row pointer (tap offset) and padding taps are zeroed when the tile is written to LDS
+// (not when it is loaded: that would make the wave wait for its own prefetch).  VAR bit 0: the pipelined loop (serial:
+// development library, DV3_L16_LOOP=0).  Epilogue (VAR bit 1): the output pixel of a row is decoded once per row
+// (shifts when H and W are powers of two, one division pair per row otherwise) instead of once per element, the reads
+// of y the accumulate path needs are issued per row block ahead of the stores, and the stores go out together (serial
+// form: DV3_L16_EPI=0, development library).
 // ------------------------------------------------------------------------------------------------
 // TR = false: conv_s2 (rows = output pixels, K = 16 Ci, taps (ky, kx), input at (2oy-1+ky, 2ox-1+kx)).
 // TR = true : convT_s2, one parity class (py, px) = blockIdx.y per grid row (rows = INPUT pixels (y, x), K = 4 Ci, taps
 //             (a, b), input at (y+py-a, x+px-b), weights wp[cls][Co][4 Ci], output pixel (2y+py, 2x+px); + bias, + out_add).
 template <int BM, int BN, bool TR, int VAR = 3>
 __global__ __launch_bounds__(256) void conv_s2_l16_kernel(ConvParams p) {
-  constexpr int BK = 32, LD = 40;
-  constexpr int WM = 2, WN = 2;                // waves: 2 x 2
   constexpr int TM = BM / 32, TN = BN / 32;    // 16 x 16 blocks per wave
-  constexpr int NA = BM * (BK / 4) / 256, NB = BN * (BK / 4) / 256;
-  static_assert(BM % 32 == 0 && BN % 32 == 0 && NA >= 1 && NB >= 1, "tile");
-  __shared__ __attribute__((aligned(16))) float As[2][BM * LD];
-  __shared__ __attribute__((aligned(16))) float Bs[2][BN * LD];
+  __shared__ __attribute__((aligned(16))) float As[2][BM * L16_LD];
+  __shared__ __attribute__((aligned(16))) float Bs[2][BN * L16_LD];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int i = lane & 15, q = lane >> 4;
-  const int wm = wave / WN, wn = wave % WN;
-  static_assert(WM * WN == 4, "four waves");
+  const int wm = wave >> 1, wn = wave & 1;
   int cls = 0, lin = blockIdx.x;
   if constexpr (TR) {
     if (!convT_tile_class(p.tiles_m * p.tiles_n, lin, cls)) return;  // whole workgroup, before any barrier
@@ -1385,13 +1374,15 @@ __global__ __launch_bounds__(256) void conv_s2_l16_kernel(ConvParams p) {
   const int tm = lin / p.tiles_n, tn = lin % p.tiles_n;
   const long m0 = (long)tm * BM;
   const int n0 = tn * BN;
-  const int c4 = (tid & 7) * 4;
+  // the stage: one tap of 32 channels per K-tile, a row pointer per staged pixel; weights of class cls
+  constexpr int NA = l16_slots<BM>, NB = l16_slots<BN>;
+  const int c4 = l16_stage_k(tid);
   const float* abase[NA];
   int iy0[NA], ix0[NA];
   bool rowok[NA];
 #pragma unroll
   for (int j = 0; j < NA; ++j) {
-    const long m = m0 + ((tid + 256 * j) >> 3);
+    const long m = m0 + l16_stage_row(tid, j);
     rowok[j] = m < M;
     const long mm = rowok[j] ? m : 0;
     const int rx = (int)(mm % RW);
@@ -1405,13 +1396,12 @@ __global__ __launch_bounds__(256) void conv_s2_l16_kernel(ConvParams p) {
   const float* bsrc[NB];
 #pragma unroll
   for (int j = 0; j < NB; ++j) {
-    const int col = n0 + ((tid + 256 * j) >> 3);
+    const int col = n0 + l16_stage_row(tid, j);
     bsrc[j] = p.wp + (long)cls * p.Co * K + (long)(col < p.Co ? col : 0) * K + c4;
   }
   f32x4 ra[NA], rb[NB];
   bool aok[NA];
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-  auto gload = [&](int k0) {
+  auto load = [&](int, int k0) {
     const int tap = k0 / p.Ci, ci0 = k0 - tap * p.Ci;
     const int ty = TR ? -(tap >> 1) : (tap >> 2), tx = TR ? -(tap & 1) : (tap & 3);
 #pragma unroll
@@ -1424,94 +1414,23 @@ __global__ __launch_bounds__(256) void conv_s2_l16_kernel(ConvParams p) {
 #pragma unroll
     for (int j = 0; j < NB; ++j) rb[j] = *reinterpret_cast<const f32x4*>(bsrc[j] + k0);
   };
-  auto lstore = [&](int buf) {
-#pragma unroll
-    for (int j = 0; j < NA; ++j)
-      *reinterpret_cast<f32x4*>(&As[buf][((tid + 256 * j) >> 3) * LD + c4]) = aok[j] ? ra[j] : zero4;
-#pragma unroll
-    for (int j = 0; j < NB; ++j) *reinterpret_cast<f32x4*>(&Bs[buf][((tid + 256 * j) >> 3) * LD + c4]) = rb[j];
+  auto store = [&](int, float* as, float* bs) {
+    l16_lds_write<(VAR & 1) != 0>(as, ra, aok, tid);  // padding taps and rows past the edge: zeros
+    l16_lds_write<(VAR & 1) != 0>(bs, rb, tid);
   };
   f32x4 acc[TM][TN];
-#pragma unroll
-  for (int a = 0; a < TM; ++a)
-#pragma unroll
-    for (int b = 0; b < TN; ++b) acc[a][b] = zero4;
-  const int nk = K / BK;
-  gload(0);
-  lstore(0);
-  if constexpr (VAR & 1) {
-    if (nk > 1) gload(BK);
-  }
-  __syncthreads();
-  const int aoff = (wm * (16 * TM) + i) * LD + 4 * q;
-  const int boff = (wn * (16 * TN) + i) * LD + 4 * q;
-  if constexpr (VAR & 1) {
-    f32x4 af[2][TM], bf[2][TN];
-    auto fread = [&](int s, int buf, int kk) {
-#pragma unroll
-      for (int a = 0; a < TM; ++a) af[s][a] = *reinterpret_cast<const f32x4*>(&As[buf][aoff + 16 * a * LD + 16 * kk]);
-#pragma unroll
-      for (int b = 0; b < TN; ++b) bf[s][b] = *reinterpret_cast<const f32x4*>(&Bs[buf][boff + 16 * b * LD + 16 * kk]);
-    };
-    auto mma = [&](int s, int g0, int g1) {
-#pragma unroll
-      for (int g = g0; g < g1; ++g)
-#pragma unroll
-        for (int a = 0; a < TM; ++a)
-#pragma unroll
-          for (int b = 0; b < TN; ++b)
-            acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[s][a][g], bf[s][b][g], acc[a][b], 0, 0, 0);
-    };
-    fread(0, 0, 0);
-    // K-tiles 0 .. nk-2: tile t+1 is already in the staging registers (prologue / the loads issued during tile t-1)
-    for (int t = 0; t + 1 < nk; ++t) {
-      const int cur = t & 1;
-      fread(1, cur, 1);
-      mma(0, 0, 2);
-      lstore(cur ^ 1);  // mid-chunk: the writes land while the second half multiplies
-      if (t + 2 < nk) gload((t + 2) * BK);
-      mma(0, 2, 4);
-      __syncthreads();
-      fread(0, cur ^ 1, 0);
-      mma(1, 0, 4);
-    }
-    // drain: the last K-tile has nothing to stage and needs no barrier
-    fread(1, (nk - 1) & 1, 1);
-    mma(0, 0, 4);
-    mma(1, 0, 4);
-  } else
-  for (int t = 0; t < nk; ++t) {
-    const int cur = t & 1;
-    if (t + 1 < nk) gload((t + 1) * BK);
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      f32x4 af[TM], bf[TN];
-#pragma unroll
-      for (int a = 0; a < TM; ++a) af[a] = *reinterpret_cast<const f32x4*>(&As[cur][aoff + 16 * a * LD + 16 * kk]);
-#pragma unroll
-      for (int b = 0; b < TN; ++b) bf[b] = *reinterpret_cast<const f32x4*>(&Bs[cur][boff + 16 * b * LD + 16 * kk]);
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-#pragma unroll
-        for (int a = 0; a < TM; ++a)
-#pragma unroll
-          for (int b = 0; b < TN; ++b)
-            acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[a][g], bf[b][g], acc[a][b], 0, 0, 0);
-    }
-    if (t + 1 < nk) lstore(cur ^ 1);
-    __syncthreads();
-  }
+  l16_mainloop<BM, BN, (VAR & 1) != 0, 1>(load, store, As, Bs, wm, wn, lane, K / L16_BK, acc);
   if constexpr (VAR & 2) {
     // a lane's TM x TN x 4 outputs are distinct addresses: the reads of y need not wait for the lane's own stores
     float add[TN];
     bool colok[TN];
 #pragma unroll
     for (int b = 0; b < TN; ++b) {
-      const int col = n0 + wn * (16 * TN) + 16 * b + i;
+      const int col = n0 + l16_acc_col<BN>(wn, b, i);
       colok[b] = col < p.Co;
       add[b] = TR ? ((p.bias && colok[b]) ? p.bias[col] : 0.f) + p.out_add : 0.f;
     }
-    float* const ycol = p.y + n0 + wn * (16 * TN) + i;  // + 16 b per column block
+    float* const ycol = p.y + n0 + l16_acc_col<BN>(wn, 0, i);  // + 16 b per column block
     const bool pow2 = (p.W & (p.W - 1)) == 0 && (p.H & (p.H - 1)) == 0;  // uniform
     const int sw = 31 - __builtin_clz(p.W), sh = 31 - __builtin_clz(p.H);
     // element offset of row `row` in y (without the column); row < M
@@ -1537,7 +1456,7 @@ __global__ __launch_bounds__(256) void conv_s2_l16_kernel(ConvParams p) {
     auto prep = [&](int s, int a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const long row = m0 + wm * (16 * TM) + 16 * a + 4 * q + r;
+        const long row = m0 + l16_acc_row<BM>(wm, a, q, r);
         off[s][r] = row < M ? rowoff(row) : -1;
         if (p.accumulate) {
 #pragma unroll
@@ -1564,12 +1483,12 @@ __global__ __launch_bounds__(256) void conv_s2_l16_kernel(ConvParams p) {
   for (int a = 0; a < TM; ++a)
 #pragma unroll
     for (int b = 0; b < TN; ++b) {
-      const int col = n0 + wn * (16 * TN) + 16 * b + i;
+      const int col = n0 + l16_acc_col<BN>(wn, b, i);
       if (col >= p.Co) continue;
       const float add = TR ? (p.bias ? p.bias[col] : 0.f) + p.out_add : 0.f;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const long row = m0 + wm * (16 * TM) + 16 * a + 4 * q + r;
+        const long row = m0 + l16_acc_row<BM>(wm, a, q, r);
         if (row < M) {
           float* o;
           if (TR) {
@@ -1753,19 +1672,10 @@ extern "C" int dv3_im2col_s2(const float* x, float* cols, int Nimg, int H, int W
 
 // conv_s2_l16_kernel launch; the development library can take the serial K loop and / or the serial epilogue
 // (DV3_L16_LOOP=0, DV3_L16_EPI=0: A/B of each mechanism on its own)
-#ifdef DV3_DEV_SWITCHES
-#define DV3_CONV_L16_LAUNCH(BM_, BN_, TR_)                                                                   \
-  do {                                                                                                       \
-    static const int var_ = (DV3_ENV_INT("DV3_L16_LOOP", 1) ? 1 : 0) | (DV3_ENV_INT("DV3_L16_EPI", 1) ? 2 : 0); \
-    if (var_ == 0) hipLaunchKernelGGL((conv_s2_l16_kernel<BM_, BN_, TR_, 0>), grid, dim3(256), 0, s, p);      \
-    else if (var_ == 1) hipLaunchKernelGGL((conv_s2_l16_kernel<BM_, BN_, TR_, 1>), grid, dim3(256), 0, s, p); \
-    else if (var_ == 2) hipLaunchKernelGGL((conv_s2_l16_kernel<BM_, BN_, TR_, 2>), grid, dim3(256), 0, s, p); \
-    else hipLaunchKernelGGL((conv_s2_l16_kernel<BM_, BN_, TR_, 3>), grid, dim3(256), 0, s, p);               \
-  } while (0)
-#else
-#define DV3_CONV_L16_LAUNCH(BM_, BN_, TR_) \
-  hipLaunchKernelGGL((conv_s2_l16_kernel<BM_, BN_, TR_, 3>), grid, dim3(256), 0, s, p)
-#endif
+#define DV3_CONV_L16_LAUNCH(BM_, BN_, TR_)                                                                       \
+  l16_with_var<3>([&](auto var) {                                                                                \
+    hipLaunchKernelGGL((conv_s2_l16_kernel<BM_, BN_, TR_, decltype(var)::value>), grid, dim3(256), 0, s, p);    \
+  })
 
 extern "C" int dv3_conv_s2_fwd(const float* x, const float* w_packed, float* y, int Nimg, int H, int W, int Ci, int Co,
                                int accumulate, void* stream) {

@@ -14,6 +14,7 @@
 #include <stdlib.h>
 
 #include "mfma_gemm.h"
+#include "l16_tile.h"
 #include "dv3_common.h"
 
 namespace dv3 {
@@ -695,263 +696,170 @@ static void launch_direct(const GemmParams& p, hipStream_t s) {
   else launch_direct_rn<TB, 4>(p, waves, s);
 }
 
+// Sampling epilogue of gemm_l16_kernel (EPI 1; as gemm_direct_kernel EPI 1; 32 x 64 tile only): a wave's 16 x 32 tile
+// is one whole categorical group of 16 rows, lane (i, q) holding classes i and 16 + i of rows 4q .. 4q+3, so the softmax,
+// the p_hat / q argmax and the one-hot stay in registers (four xor-shuffles per reduction, the four rows of a
+// lane interleaved).  Same reduction order as dv3_onehot_sample_fwd: class d first meets d ^ 16 (the lane's
+// other register), then d ^ 8 .. d ^ 1 -- the sample is bit-equal to the two-launch form.
+template <int BM, int BN>
+__device__ __forceinline__ void l16_sample_epilogue(const GemmParams& p, const f32x4 (&acc)[BM / 32][BN / 32], int m0,
+                                                    int n0, int wm, int wn, int i, int q) {
+  static_assert(BM == 32 && BN == 64, "sampling epilogue: 32 x 64 tile");
+  const int S = p.N >> 5;
+  const int colb = n0 + l16_acc_col<BN>(wn, 0, 0);
+  if (colb >= p.N) return;  // wave-uniform; no barrier follows
+  unsigned long long seed = 0, offset = 0;
+  if (!p.smp_mode && !p.smp_noise) {
+    seed = p.smp_rng[0];
+    offset = p.smp_rng[1] + p.smp_off;
+  }
+  const float bias0 = p.bias ? p.bias[colb + i] : 0.f, bias1 = p.bias ? p.bias[colb + 16 + i] : 0.f;
+  float l0[4], l1[4], mx[4], e0[4], e1[4], sm[4], sc[4];
+  int bi[4];
+  long gi[4];
+  bool rv[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int row = m0 + l16_acc_row<BM>(wm, 0, q, r);
+    rv[r] = row < p.M;
+    gi[r] = (long)row * S + (colb >> 5);
+    l0[r] = acc[0][0][r] + bias0;
+    l1[r] = acc[0][1][r] + bias1;
+    if (rv[r]) {
+      float* o = p.C + (long)row * p.ldc + colb + i;
+      o[0] = l0[r];
+      o[16] = l1[r];
+    }
+    mx[r] = fmaxf(l0[r], l1[r]);
+  }
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) mx[r] = fmaxf(mx[r], __shfl_xor(mx[r], o, 64));
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    e0[r] = expf(l0[r] - mx[r]);
+    e1[r] = expf(l1[r] - mx[r]);
+    sm[r] = e0[r] + e1[r];
+  }
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) sm[r] += __shfl_xor(sm[r], o, 64);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const float ph0 = (e0[r] / sm[r]) * (1.f - p.smp_unimix) + p.smp_unimix / 32.f;
+    const float ph1 = (e1[r] / sm[r]) * (1.f - p.smp_unimix) + p.smp_unimix / 32.f;
+    float s0 = ph0, s1 = ph1;
+    if (!p.smp_mode) {
+      float q0, q1;
+      if (p.smp_noise) {
+        q0 = rv[r] ? p.smp_noise[gi[r] * 32 + i] : 1.f;
+        q1 = rv[r] ? p.smp_noise[gi[r] * 32 + 16 + i] : 1.f;
+      } else {
+        uint32_t o4[4];
+        const unsigned long long ea = (unsigned long long)gi[r] * 32 + i, eb = ea + 16;
+        Philox ph4(seed);
+        ph4(offset + (ea >> 2), 0x5eedULL, o4);
+        q0 = fmaxf(-logf(u01(o4[ea & 3])), 1e-30f);
+        ph4(offset + (eb >> 2), 0x5eedULL, o4);
+        q1 = fmaxf(-logf(u01(o4[eb & 3])), 1e-30f);
+      }
+      s0 = ph0 / q0;
+      s1 = ph1 / q1;
+    }
+    const bool hi = s1 > s0;  // tie: the lower class index
+    sc[r] = hi ? s1 : s0;
+    bi[r] = hi ? 16 + i : i;
+  }
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float ob = __shfl_xor(sc[r], o, 64);
+      const int oi = __shfl_xor(bi[r], o, 64);
+      if (ob > sc[r] || (ob == sc[r] && oi < bi[r])) {
+        sc[r] = ob;
+        bi[r] = oi;
+      }
+    }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    if (p.smp_forced) {
+      const int f = rv[r] ? p.smp_forced[gi[r]] : 0;
+      if (rv[r] && i == 0 && p.smp_flips && f != bi[r]) atomicAdd(p.smp_flips, 1u);
+      bi[r] = f;
+    }
+    if (rv[r]) {
+      float* o = p.smp_onehot + gi[r] * 32 + i;
+      o[0] = (i == bi[r]) ? 1.f : 0.f;
+      o[16] = (16 + i == bi[r]) ? 1.f : 0.f;
+      if (i == 0 && p.smp_idx) p.smp_idx[gi[r]] = bi[r];
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // LDS-tiled y = [A|A2] W^T (+ bias) -- tiles 11-15: the mid-size and large products of the path (the 1024-row
-// imagination GEMMs up to 4096 x 12288 x 5120) -- v_mfma_f32_16x16x4_f32 with BOTH operands kept k-contiguous in LDS:
-// a lane's MFMA fragment for four consecutive k steps is one ds_read_b128 (row i = l & 15, k = 16 kk + 4 (l >> 4) .. +3)
-// and a staged float4 is one ds_write_b128 -- a quarter of the LDS instructions of the k-major 32x32x2 tile engine (no
-// transposing ds_write_b32), and every loaded element is reused BN/32 (A) or BM/32 (B) times from registers.
-// Row stride 40 floats: the 16 lanes a ds_read_b128 serves together (0-3, 12-15, 20-27 | ...) then cover all 64
-// banks exactly once (i*40 + 4q mod 64 is a permutation of the 16 four-bank windows), and the 8 lanes of a
-// ds_write_b128 group write 128 contiguous bytes.  One workgroup = 4 waves (2 x 2) = one BM x BN tile, BK = 32,
-// double-buffered, one barrier per K-tile.  The K loop is software-pipelined inside the wave (VAR bit 0): two fragment
-// sets, so that the ds_read_b128 of the next 16-k chunk, the ds_write_b128 of the next K-tile and the global loads of
-// the tile after it are all issued with MFMAs of the same wave behind them:
-//   reads (t, 1) | MFMAs (t, 0) g 0-1 | ds_write t+1 -> cur^1 | global loads t+2 | MFMAs (t, 0) g 2-3 | barrier |
-//   reads (t+1, 0) | MFMAs (t, 1)
-// (the barrier of t-1 came after every read of cur^1; every read of cur is complete at the barrier of t).  Each
-// accumulator still receives its MFMAs in ascending (t, kk, g): bit-equal to the serial loop (VAR bit 0 clear: read,
-// wait, multiply per chunk), which the 128 x 128 tile keeps (launch_l16) and the development library can select for
-// every tile (DV3_L16_LOOP=0).
-// Epilogue (VAR bit 1): per row block a, every C element the accumulate path needs is loaded (those of block a + 1
-// before the stores of block a) and the stores are issued together; the serial form (DV3_L16_EPI=0, development
-// library) reads, adds and stores one element at a time, each waiting for the store before it.
+// imagination GEMMs up to 4096 x 12288 x 5120) -- on the k-contiguous LDS tile engine of l16_tile.h (scheme, K loop
+// and accumulator map are described there).  VAR bit 0: the pipelined loop, which every tile takes but 128 x 128
+// (launch_l16).  VAR bit 1: the batched epilogue -- per row block a, every C element the accumulate path needs is
+// loaded (those of block a + 1 before the stores of block a) and the stores are issued together; the serial form
+// (DV3_L16_EPI=0, development library) reads, adds and stores one element at a time, each waiting for the store
+// before it.
 // Tile shapes 32x64 / 64x64 / 64x96 / 128x128, picked by output size (launch_l16 / pick_tile; measurements in
 // dv3hip/ops.py pick_gemm_tile).  Tile order: xcd_tile (each XCD owns a block of tiles chosen by operand bytes).
 // Requires K % 32 == 0, K1 % 32 == 0, lda/lda2/ldb % 4 == 0, 16-byte aligned operands (l16_ok).
 // ------------------------------------------------------------------------------------------------
 template <int BM, int BN, int PF, int EPI = 0, int VAR = 3>
 __global__ __launch_bounds__(256) void gemm_l16_kernel(GemmParams p) {
-  static_assert(PF == 1 || !(VAR & 1), "the pipelined loop has one staging register set");
-  constexpr int BK = 32, LD = 40;
   constexpr int TMW = BM / 32, TNW = BN / 32;  // 16 x 16 blocks per wave (wave tile = BM/2 x BN/2)
-  constexpr int NA = BM * (BK / 4) / 256, NB = BN * (BK / 4) / 256;
-  static_assert(BM % 32 == 0 && BN % 32 == 0 && NA >= 1 && NB >= 1, "tile");
-  __shared__ __attribute__((aligned(16))) float As[2][BM * LD];
-  __shared__ __attribute__((aligned(16))) float Bs[2][BN * LD];
+  __shared__ __attribute__((aligned(16))) float As[2][BM * L16_LD];
+  __shared__ __attribute__((aligned(16))) float Bs[2][BN * L16_LD];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int i = lane & 15, q = lane >> 4;
   const int wm = wave >> 1, wn = wave & 1;
   int tm, tn;
   xcd_tile(p, blockIdx.x, tm, tn);
   const int m0 = tm * BM, n0 = tn * BN;
-  // staging: float4 f = tid + 256 j of a [rows][8] grid -> row f >> 3, k offset 4 (f & 7).  Rows past the edge of
+  // the stage: rows of A (k < K1) or A2 (k >= K1; the seam sits on a K-tile edge) and of W.  Rows past the edge of
   // the matrix read row 0 instead: they only feed outputs past the edge, which the epilogue does not store (no
   // masking of the loaded values, which would make the wave wait for its prefetch as soon as it is issued).
+  constexpr int NA = l16_slots<BM>, NB = l16_slots<BN>;
   const float* asrc[NA];
   const float* asrc2[NA];
   const float* bsrc[NB];
-  const int c4 = (tid & 7) * 4;
+  const int c4 = l16_stage_k(tid);
 #pragma unroll
   for (int j = 0; j < NA; ++j) {
-    const int row = m0 + ((tid + 256 * j) >> 3);
+    const int row = m0 + l16_stage_row(tid, j);
     asrc[j] = p.A + (long)(row < p.M ? row : 0) * p.lda + c4;
     asrc2[j] = p.A2 ? p.A2 + (long)(row < p.M ? row : 0) * p.lda2 + c4 : nullptr;
   }
 #pragma unroll
   for (int j = 0; j < NB; ++j) {
-    const int col = n0 + ((tid + 256 * j) >> 3);
+    const int col = n0 + l16_stage_row(tid, j);
     bsrc[j] = p.B + (long)(col < p.N ? col : 0) * p.ldb + c4;
   }
-  // PF register sets: the loads of K-tile t + PF are in flight while tile t is multiplied.  Measured (1024-row
-  // shapes): PF 2 / 4 equal PF 1 within noise -- the default; the template parameter stays for longer-latency operands.
   f32x4 ra[PF][NA], rb[PF][NB];
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-  auto gload = [&](f32x4 (&xa)[NA], f32x4 (&xb)[NB], int k0) {
+  auto load = [&](int slot, int k0) {
     const bool seg2 = k0 >= p.K1;
 #pragma unroll
     for (int j = 0; j < NA; ++j)
-      xa[j] = *reinterpret_cast<const f32x4*>(seg2 ? asrc2[j] + (k0 - p.K1) : asrc[j] + k0);
+      ra[slot][j] = *reinterpret_cast<const f32x4*>(seg2 ? asrc2[j] + (k0 - p.K1) : asrc[j] + k0);
 #pragma unroll
-    for (int j = 0; j < NB; ++j) xb[j] = *reinterpret_cast<const f32x4*>(bsrc[j] + k0);
+    for (int j = 0; j < NB; ++j) rb[slot][j] = *reinterpret_cast<const f32x4*>(bsrc[j] + k0);
   };
-  auto lstore = [&](const f32x4 (&xa)[NA], const f32x4 (&xb)[NB], int buf) {
-#pragma unroll
-    for (int j = 0; j < NA; ++j)
-      *reinterpret_cast<f32x4*>(&As[buf][((tid + 256 * j) >> 3) * LD + c4]) = xa[j];
-#pragma unroll
-    for (int j = 0; j < NB; ++j)
-      *reinterpret_cast<f32x4*>(&Bs[buf][((tid + 256 * j) >> 3) * LD + c4]) = xb[j];
+  auto store = [&](int slot, float* as, float* bs) {
+    l16_lds_write<(VAR & 1) != 0>(as, ra[slot], tid);
+    l16_lds_write<(VAR & 1) != 0>(bs, rb[slot], tid);
   };
   f32x4 acc[TMW][TNW];
-#pragma unroll
-  for (int a = 0; a < TMW; ++a)
-#pragma unroll
-    for (int b = 0; b < TNW; ++b) acc[a][b] = zero4;
-  const int nk = p.K / BK;
-  gload(ra[0], rb[0], 0);
-  lstore(ra[0], rb[0], 0);
-#pragma unroll
-  for (int u = 1; u < PF; ++u)
-    if (u < nk) gload(ra[u], rb[u], u * BK);
-  if constexpr (VAR & 1) {
-    if (nk > 1) gload(ra[0], rb[0], BK);
-  }
-  __syncthreads();
-  const int aoff = (wm * (BM / 2) + i) * LD + 4 * q;
-  const int boff = (wn * (BN / 2) + i) * LD + 4 * q;
-  if constexpr (VAR & 1) {
-    f32x4 af[2][TMW], bf[2][TNW];
-    auto fread = [&](int s, int buf, int kk) {
-#pragma unroll
-      for (int a = 0; a < TMW; ++a) af[s][a] = *reinterpret_cast<const f32x4*>(&As[buf][aoff + 16 * a * LD + 16 * kk]);
-#pragma unroll
-      for (int b = 0; b < TNW; ++b) bf[s][b] = *reinterpret_cast<const f32x4*>(&Bs[buf][boff + 16 * b * LD + 16 * kk]);
-    };
-    auto mma = [&](int s, int g0, int g1) {
-#pragma unroll
-      for (int g = g0; g < g1; ++g)
-#pragma unroll
-        for (int a = 0; a < TMW; ++a)
-#pragma unroll
-          for (int b = 0; b < TNW; ++b)
-            acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[s][a][g], bf[s][b][g], acc[a][b], 0, 0, 0);
-    };
-    fread(0, 0, 0);
-    // K-tiles 0 .. nk-2: tile t+1 is already in the staging registers (prologue above / step 4 of tile t-1)
-    for (int t = 0; t + 1 < nk; ++t) {
-      const int cur = t & 1;
-      fread(1, cur, 1);
-      mma(0, 0, 2);
-      lstore(ra[0], rb[0], cur ^ 1);  // mid-chunk: the writes land while the second half multiplies
-      if (t + 2 < nk) gload(ra[0], rb[0], (t + 2) * BK);
-      mma(0, 2, 4);
-      __syncthreads();
-      fread(0, cur ^ 1, 0);
-      mma(1, 0, 4);
-    }
-    // drain: the last K-tile (the only one when nk == 1) has nothing to stage and needs no barrier
-    fread(1, (nk - 1) & 1, 1);
-    mma(0, 0, 4);
-    mma(1, 0, 4);
-  } else
-  for (int t0 = 0; t0 < nk; t0 += PF)
-#pragma unroll
-  for (int u = 0; u < PF; ++u) {
-    const int t = t0 + u;
-    if (t >= nk) break;
-    const int cur = t & 1;
-    if (t + PF < nk) gload(ra[u], rb[u], (t + PF) * BK);
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      f32x4 af[TMW], bf[TNW];
-#pragma unroll
-      for (int a = 0; a < TMW; ++a) af[a] = *reinterpret_cast<const f32x4*>(&As[cur][aoff + 16 * a * LD + 16 * kk]);
-#pragma unroll
-      for (int b = 0; b < TNW; ++b) bf[b] = *reinterpret_cast<const f32x4*>(&Bs[cur][boff + 16 * b * LD + 16 * kk]);
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-#pragma unroll
-        for (int a = 0; a < TMW; ++a)
-#pragma unroll
-          for (int b = 0; b < TNW; ++b)
-            acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[a][g], bf[b][g], acc[a][b], 0, 0, 0);
-    }
-    if (t + 1 < nk) lstore(ra[(u + 1) % PF], rb[(u + 1) % PF], cur ^ 1);
-    __syncthreads();
-  }
+  l16_mainloop<BM, BN, (VAR & 1) != 0, PF>(load, store, As, Bs, wm, wn, lane, p.K / L16_BK, acc);
   if constexpr (EPI == 1) {
-    // Sampling epilogue (as gemm_direct_kernel EPI 1; 32 x 64 tile only): a wave's 16 x 32 tile is one whole
-    // categorical group of 16 rows, lane (i, q) holding classes i and 16 + i of rows 4q .. 4q+3, so the softmax,
-    // the p_hat / q argmax and the one-hot stay in registers (four xor-shuffles per reduction, the four rows of a
-    // lane interleaved).  Same reduction order as dv3_onehot_sample_fwd: class d first meets d ^ 16 (the lane's
-    // other register), then d ^ 8 .. d ^ 1 -- the sample is bit-equal to the two-launch form.
-    static_assert(BM == 32 && BN == 64, "sampling epilogue: 32 x 64 tile");
-    const int S = p.N >> 5;
-    const int colb = n0 + wn * 32;
-    if (colb >= p.N) return;  // wave-uniform; no barrier follows
-    unsigned long long seed = 0, offset = 0;
-    if (!p.smp_mode && !p.smp_noise) {
-      seed = p.smp_rng[0];
-      offset = p.smp_rng[1] + p.smp_off;
-    }
-    const float bias0 = p.bias ? p.bias[colb + i] : 0.f, bias1 = p.bias ? p.bias[colb + 16 + i] : 0.f;
-    float l0[4], l1[4], mx[4], e0[4], e1[4], sm[4], sc[4];
-    int bi[4];
-    long gi[4];
-    bool rv[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = m0 + wm * 16 + 4 * q + r;
-      rv[r] = row < p.M;
-      gi[r] = (long)row * S + (colb >> 5);
-      l0[r] = acc[0][0][r] + bias0;
-      l1[r] = acc[0][1][r] + bias1;
-      if (rv[r]) {
-        float* o = p.C + (long)row * p.ldc + colb + i;
-        o[0] = l0[r];
-        o[16] = l1[r];
-      }
-      mx[r] = fmaxf(l0[r], l1[r]);
-    }
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) mx[r] = fmaxf(mx[r], __shfl_xor(mx[r], o, 64));
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      e0[r] = expf(l0[r] - mx[r]);
-      e1[r] = expf(l1[r] - mx[r]);
-      sm[r] = e0[r] + e1[r];
-    }
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) sm[r] += __shfl_xor(sm[r], o, 64);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float ph0 = (e0[r] / sm[r]) * (1.f - p.smp_unimix) + p.smp_unimix / 32.f;
-      const float ph1 = (e1[r] / sm[r]) * (1.f - p.smp_unimix) + p.smp_unimix / 32.f;
-      float s0 = ph0, s1 = ph1;
-      if (!p.smp_mode) {
-        float q0, q1;
-        if (p.smp_noise) {
-          q0 = rv[r] ? p.smp_noise[gi[r] * 32 + i] : 1.f;
-          q1 = rv[r] ? p.smp_noise[gi[r] * 32 + 16 + i] : 1.f;
-        } else {
-          uint32_t o4[4];
-          const unsigned long long ea = (unsigned long long)gi[r] * 32 + i, eb = ea + 16;
-          Philox ph4(seed);
-          ph4(offset + (ea >> 2), 0x5eedULL, o4);
-          q0 = fmaxf(-logf(u01(o4[ea & 3])), 1e-30f);
-          ph4(offset + (eb >> 2), 0x5eedULL, o4);
-          q1 = fmaxf(-logf(u01(o4[eb & 3])), 1e-30f);
-        }
-        s0 = ph0 / q0;
-        s1 = ph1 / q1;
-      }
-      const bool hi = s1 > s0;  // tie: the lower class index
-      sc[r] = hi ? s1 : s0;
-      bi[r] = hi ? 16 + i : i;
-    }
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float ob = __shfl_xor(sc[r], o, 64);
-        const int oi = __shfl_xor(bi[r], o, 64);
-        if (ob > sc[r] || (ob == sc[r] && oi < bi[r])) {
-          sc[r] = ob;
-          bi[r] = oi;
-        }
-      }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      if (p.smp_forced) {
-        const int f = rv[r] ? p.smp_forced[gi[r]] : 0;
-        if (rv[r] && i == 0 && p.smp_flips && f != bi[r]) atomicAdd(p.smp_flips, 1u);
-        bi[r] = f;
-      }
-      if (rv[r]) {
-        float* o = p.smp_onehot + gi[r] * 32 + i;
-        o[0] = (i == bi[r]) ? 1.f : 0.f;
-        o[16] = (16 + i == bi[r]) ? 1.f : 0.f;
-        if (i == 0 && p.smp_idx) p.smp_idx[gi[r]] = bi[r];
-      }
-    }
+    l16_sample_epilogue<BM, BN>(p, acc, m0, n0, wm, wn, i, q);
     return;
   }
-  // accumulator register r of block (a, b): row 16 a + 4 q + r, column 16 b + i
   if constexpr (VAR & 2) {
     // a lane's TMW x TNW x 4 outputs are distinct addresses: the reads of C need not wait for the lane's own stores
     float bv[TNW];
@@ -960,7 +868,7 @@ __global__ __launch_bounds__(256) void gemm_l16_kernel(GemmParams p) {
     bool accf[TNW];
 #pragma unroll
     for (int b = 0; b < TNW; ++b) {
-      const int col = n0 + wn * (BN / 2) + 16 * b + i;
+      const int col = n0 + l16_acc_col<BN>(wn, b, i);
       const bool ok = col < p.N;
       const bool second = p.C2 && col >= p.nsplit;
       bv[b] = (ok && p.bias) ? p.bias[col] : 0.f;
@@ -972,7 +880,7 @@ __global__ __launch_bounds__(256) void gemm_l16_kernel(GemmParams p) {
     auto cload = [&](int s, int a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int row = m0 + wm * (BM / 2) + 16 * a + 4 * q + r;
+        const int row = m0 + l16_acc_row<BM>(wm, a, q, r);
 #pragma unroll
         for (int b = 0; b < TNW; ++b) cv[s][b][r] = (accf[b] && row < p.M) ? cbase[b][(long)row * ldo[b]] : 0.f;
       }
@@ -984,7 +892,7 @@ __global__ __launch_bounds__(256) void gemm_l16_kernel(GemmParams p) {
       if (any_acc && a + 1 < TMW) cload((a + 1) & 1, a + 1);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int row = m0 + wm * (BM / 2) + 16 * a + 4 * q + r;
+        const int row = m0 + l16_acc_row<BM>(wm, a, q, r);
 #pragma unroll
         for (int b = 0; b < TNW; ++b) {
           float v = acc[a][b][r] + bv[b];
@@ -999,7 +907,7 @@ __global__ __launch_bounds__(256) void gemm_l16_kernel(GemmParams p) {
   for (int a = 0; a < TMW; ++a)
 #pragma unroll
     for (int b = 0; b < TNW; ++b) {
-      const int col = n0 + wn * (BN / 2) + 16 * b + i;
+      const int col = n0 + l16_acc_col<BN>(wn, b, i);
       if (col >= p.N) continue;
       const float bv = p.bias ? p.bias[col] : 0.f;
       const bool second = p.C2 && col >= p.nsplit;
@@ -1008,7 +916,7 @@ __global__ __launch_bounds__(256) void gemm_l16_kernel(GemmParams p) {
       const int accf = second ? p.accumulate2 : p.accumulate;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int row = m0 + wm * (BM / 2) + 16 * a + 4 * q + r;
+        const int row = m0 + l16_acc_row<BM>(wm, a, q, r);
         if (row < p.M) {
           float* o = cbase + (long)row * ldo;
           float v = acc[a][b][r] + bv;
@@ -1027,8 +935,7 @@ static void launch_l16_sample(const GemmParams& p0, hipStream_t s) {
   pick_xcd_grid(p);
   const dim3 grid(p.tiles_m * p.tiles_n), block(256);
 #ifdef DV3_DEV_SWITCHES
-  static const int loop = DV3_ENV_INT("DV3_L16_LOOP", 1);
-  if (!loop) {
+  if (!(l16_var(3) & 1)) {  // (EPI 1 has one epilogue: VAR bit 1 stays set)
     hipLaunchKernelGGL((gemm_l16_kernel<32, 64, 1, 1, 2>), grid, block, 0, s, p);
     return;
   }
@@ -1040,6 +947,25 @@ static bool l16_ok(const GemmParams& p, int transA, int transB) {
   return !transA && transB && p.K >= 32 && (p.K % 32) == 0 && (p.K1 % 32) == 0 && (p.lda % 4) == 0 &&
          (!p.A2 || (p.lda2 % 4) == 0) && (p.ldb % 4) == 0 && ((uintptr_t)p.A % 16) == 0 &&
          (!p.A2 || ((uintptr_t)p.A2 % 16) == 0) && ((uintptr_t)p.B % 16) == 0;
+}
+
+// One tile shape; SHIPPED: the VAR the shipped library launches.  Development library: DV3_L16_LOOP / DV3_L16_EPI
+// (l16_var), and DV3_L16_PF=2 next to DV3_L16_LOOP=0: prefetch distance 2, which only the serial loop has.
+template <int BM, int BN, int SHIPPED>
+static void launch_l16_tile(const GemmParams& p, dim3 grid, hipStream_t s) {
+  l16_with_var<SHIPPED>([&](auto var) {
+    constexpr int VAR = decltype(var)::value;
+#ifdef DV3_DEV_SWITCHES
+    static const bool pf2 = DV3_ENV_INT("DV3_L16_PF", 1) == 2 && l16_loop_switch() == 0;
+    if constexpr (!(VAR & 1)) {
+      if (pf2) {
+        hipLaunchKernelGGL((gemm_l16_kernel<BM, BN, 2, 0, VAR>), grid, dim3(256), 0, s, p);
+        return;
+      }
+    }
+#endif
+    hipLaunchKernelGGL((gemm_l16_kernel<BM, BN, 1, 0, VAR>), grid, dim3(256), 0, s, p);
+  });
 }
 
 // tile shape: measured (tools/gemm_bench.py; 128 x 128: 4096^3 1059 us = 130 TFLOP/s against 1228 on the k-major
@@ -1059,33 +985,15 @@ static void launch_l16(const GemmParams& p0, int force, hipStream_t s) {
   p.tiles_m = (p.M + bm - 1) / bm;
   p.tiles_n = (p.N + bn - 1) / bn;
   pick_xcd_grid(p);
-  const dim3 grid(p.tiles_m * p.tiles_n), block(256);
-#define DV3_L16_LAUNCH(PFV, VARV, VAR128)                                                                  \
-  do {                                                                                                     \
-    if (sel == 1) hipLaunchKernelGGL((gemm_l16_kernel<64, 96, PFV, 0, VARV>), grid, block, 0, s, p);         \
-    else if (sel == 2) hipLaunchKernelGGL((gemm_l16_kernel<64, 64, PFV, 0, VARV>), grid, block, 0, s, p);    \
-    else if (sel == 4) hipLaunchKernelGGL((gemm_l16_kernel<128, 128, PFV, 0, VAR128>), grid, block, 0, s, p); \
-    else if (sel == 5) hipLaunchKernelGGL((gemm_l16_kernel<128, 64, PFV, 0, VARV>), grid, block, 0, s, p);   \
-    else if (sel == 6) hipLaunchKernelGGL((gemm_l16_kernel<64, 128, PFV, 0, VARV>), grid, block, 0, s, p);   \
-    else hipLaunchKernelGGL((gemm_l16_kernel<32, 64, PFV, 0, VARV>), grid, block, 0, s, p);                 \
-  } while (0)
-#ifdef DV3_DEV_SWITCHES
-  // A/B of the loop and of the epilogue, each on its own (the serial loop also keeps the prefetch-distance switch).
-  // DV3_L16_LOOP: 0 serial on every tile, 1 pipelined on every tile, unset: as shipped.
-  static const int pf = DV3_ENV_INT("DV3_L16_PF", 1);
-  static const int loop = DV3_ENV_INT("DV3_L16_LOOP", -1), epi = DV3_ENV_INT("DV3_L16_EPI", 1);
-  if (!loop && pf == 2 && epi) { DV3_L16_LAUNCH(2, 2, 2); return; }
-  if (!loop && pf == 2) { DV3_L16_LAUNCH(2, 0, 0); return; }
-  if (!loop && epi) { DV3_L16_LAUNCH(1, 2, 2); return; }
-  if (!loop) { DV3_L16_LAUNCH(1, 0, 0); return; }
-  if (loop == 1 && epi) { DV3_L16_LAUNCH(1, 3, 3); return; }
-  if (loop == 1) { DV3_L16_LAUNCH(1, 1, 1); return; }
-  if (!epi) { DV3_L16_LAUNCH(1, 1, 0); return; }
-#endif
+  const dim3 grid(p.tiles_m * p.tiles_n);
   // the 128 x 128 tile keeps the serial loop: where it is the tile of choice (two workgroups per CU, in step) the
   // pipelined loop measured no faster
-  DV3_L16_LAUNCH(1, 3, 2);
-#undef DV3_L16_LAUNCH
+  if (sel == 1) launch_l16_tile<64, 96, 3>(p, grid, s);
+  else if (sel == 2) launch_l16_tile<64, 64, 3>(p, grid, s);
+  else if (sel == 4) launch_l16_tile<128, 128, 2>(p, grid, s);
+  else if (sel == 5) launch_l16_tile<128, 64, 3>(p, grid, s);
+  else if (sel == 6) launch_l16_tile<64, 128, 3>(p, grid, s);
+  else launch_l16_tile<32, 64, 3>(p, grid, s);
 }
 
 // Register-direct weight gradient: C[M,N] += A^T B with A [K][M] and B [K][N] (both row-major over the batch

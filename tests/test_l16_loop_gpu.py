@@ -7,7 +7,11 @@ equal the float64 product cast to fp32 bit for bit, whatever the order of the su
 K chunk or epilogue element shows up exactly.  Bias, out_add and the accumulate base are multiples of 1/8 as well.
 
 Old loop against new loop: one child process runs the development library with the serial loop and the serial
-epilogue selected (DV3_L16_LOOP=0 DV3_L16_EPI=0) on random normal data; the shipped library must give the same bits."""
+epilogue selected (DV3_L16_LOOP=0 DV3_L16_EPI=0) on random normal data; the shipped library must give the same bits.
+
+Parent recording: both loops are one piece of shared code (csrc/l16_tile.h), so an error they have in common, or a
+changed order of summation, shows only against outputs recorded from the kernels as they were before the loop moved
+there (tests/golden/l16_parent*.npz, written by tests/golden/make_l16_parent_control.py)."""
 import math
 import os
 import subprocess
@@ -179,6 +183,26 @@ def test_serial_loop_of_the_development_library_gives_the_same_bits(ops, tmp_pat
     assert sorted(old) == sorted(new)
     for name, t in new.items():
         assert torch.equal(t.cpu(), old[name]), f"{name}: {int((t.cpu() != old[name]).sum())} elements differ"
+
+
+# ------------------------------------------------------------------------------------------ parent recording
+def test_l16_matches_parent_recording(ops):
+    """Random normal data, the smallest shapes that reach every phase of the loop (nk = 1, 2, 3, the [A | A2] seam) and
+    an edge tile on every tile shape: every bit as the parent commit computed it.  Not covered here: the 128-row conv
+    tiles (chosen from 448 workgroups up: tests/test_fullsize_gpu.py) and the sampling tile
+    (test_gemm_l16_sampling_tile_exact)."""
+    from tests.golden import make_l16_parent_control as parent  # (not at module level: the child process below)
+
+    path = os.path.join(REPO, "tests", "golden", "l16_parent.npz")
+    rec = parent.load(path)
+    for tile in parent.L16_TILES:
+        for name, C in parent.gemm_cases(ops, rec, tile).items():
+            assert torch.equal(C.cpu(), rec[name]), f"{name} tile {tile}: {int((C.cpu() != rec[name]).sum())} elements differ"
+    for name, C in parent.split_case(ops, rec).items():
+        assert torch.equal(C.cpu(), rec[name]), f"{name}: {int((C.cpu() != rec[name]).sum())} elements differ"
+    rec = parent.load(parent.conv_path(path))
+    for name, y in parent.conv_cases(ops, rec).items():
+        assert torch.equal(y.cpu(), rec[name]), f"{name}: {int((y.cpu() != rec[name]).sum())} elements differ"
 
 
 if __name__ == "__main__":
