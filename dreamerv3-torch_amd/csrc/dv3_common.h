@@ -39,6 +39,53 @@ __device__ __forceinline__ float dsiluf_(float x) {
   return s * (1.f + x * (1.f - s));
 }
 
+// Layer activation codes (config keys act / encoder.act / decoder.act); include/dv3hip.h documents the table and
+// dv3hip/ops.py mirrors it as ACT_CODES.  Code 1 is the compiled-in SiLU of every kernel; codes 2..6 run the same
+// kernels in their runtime-code instantiation (template parameter RT), which calls actf_ / dactf_.
+#define DV3_ACT_NONE 0
+#define DV3_ACT_SILU 1
+#define DV3_ACT_RELU 2
+#define DV3_ACT_ELU 3
+#define DV3_ACT_GELU 4
+#define DV3_ACT_TANH 5
+#define DV3_ACT_MISH 6
+static inline bool dv3_act_ok(int code) { return code >= DV3_ACT_NONE && code <= DV3_ACT_MISH; }
+// the runtime-code instantiation is taken for every code but the two today's kernels know
+static inline bool dv3_act_rt(int code) { return code > DV3_ACT_SILU; }
+
+// softplus and its tanh, finite for |z| <= 40 and beyond (exp only of non-positive arguments)
+__device__ __forceinline__ float act_softplusf_(float z) { return fmaxf(z, 0.f) + log1pf(expf(-fabsf(z))); }
+__device__ __forceinline__ float actf_(float z, int code) {
+  switch (code) {
+    case DV3_ACT_SILU: return siluf_(z);
+    case DV3_ACT_RELU: return fmaxf(z, 0.f);
+    case DV3_ACT_ELU: return z > 0.f ? z : expm1f(z);
+    case DV3_ACT_GELU: return 0.5f * z * (1.f + erff(z * 0.70710678118654752f));
+    case DV3_ACT_TANH: return tanhf(z);
+    case DV3_ACT_MISH: return z * tanhf(act_softplusf_(z));
+    default: return z;
+  }
+}
+__device__ __forceinline__ float dactf_(float z, int code) {
+  switch (code) {
+    case DV3_ACT_SILU: return dsiluf_(z);
+    case DV3_ACT_RELU: return z > 0.f ? 1.f : 0.f;
+    case DV3_ACT_ELU: return z > 0.f ? 1.f : expf(z);
+    case DV3_ACT_GELU:  // Phi(z) + z phi(z)
+      return 0.5f * (1.f + erff(z * 0.70710678118654752f)) + z * 0.3989422804014327f * expf(-0.5f * z * z);
+    case DV3_ACT_TANH: {
+      const float t = tanhf(z);
+      return 1.f - t * t;
+    }
+    case DV3_ACT_MISH: {  // tanh(sp) + z (1 - tanh(sp)^2) sigmoid(z)
+      const float t = tanhf(act_softplusf_(z));
+      const float sg = z >= 0.f ? 1.f / (1.f + expf(-z)) : expf(z) / (1.f + expf(z));
+      return t + z * (1.f - t * t) * sg;
+    }
+    default: return 1.f;
+  }
+}
+
 // reductions over a power-of-two group of G consecutive lanes (G <= 64)
 template <int G>
 __device__ __forceinline__ float group_sum(float v) {

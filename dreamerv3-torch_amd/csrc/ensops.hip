@@ -94,13 +94,13 @@ __global__ __launch_bounds__(kThreads) void ens_gemm_kernel(EnsGemmParams p) {
 // LayerNorm(eps 1e-3) + SiLU over the K*M rows of [K][M][N] with per-member gamma / beta: row r uses member r / M.
 // One wave per row, the row cached in registers (N <= 64 * NV).
 // ------------------------------------------------------------------------------------------------
-template <int NV>
+template <int NV, bool RT = false>
 __global__ __launch_bounds__(256) void ens_ln_act_fwd_kernel(const float* __restrict__ x, long ldx,
                                                              const float* __restrict__ gamma,
                                                              const float* __restrict__ beta, long sG,
                                                              float* __restrict__ y, long ldy,
                                                              float* __restrict__ mean_out,
-                                                             float* __restrict__ rstd_out, long R, int M, int N) {
+                                                             float* __restrict__ rstd_out, long R, int M, int N, int act) {
   const int l = threadIdx.x & 63;
   const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= R) return;
@@ -126,7 +126,11 @@ __global__ __launch_bounds__(256) void ens_ln_act_fwd_kernel(const float* __rest
 #pragma unroll
   for (int v = 0; v < NV; ++v) {
     const int c = l + v * 64;
-    if (c < N) y[r * ldy + c] = siluf_((xv[v] - mean) * rstd * g[c] + b[c]);
+    if constexpr (RT) {
+      if (c < N) y[r * ldy + c] = actf_((xv[v] - mean) * rstd * g[c] + b[c], act);
+    } else {
+      if (c < N) y[r * ldy + c] = siluf_((xv[v] - mean) * rstd * g[c] + b[c]);
+    }
   }
   if (l == 0) {
     mean_out[r] = mean;
@@ -136,7 +140,7 @@ __global__ __launch_bounds__(256) void ens_ln_act_fwd_kernel(const float* __rest
 
 // dx = d(loss)/d(x) given dy = d(loss)/d(SiLU(LN(x))).  grid (row blocks, members); dgamma / dbeta [K][N] are
 // ACCUMULATED (+=) with one atomicAdd per column per workgroup (the order of those adds is not fixed).
-template <int NV>
+template <int NV, bool RT = false>
 __global__ __launch_bounds__(256) void ens_ln_act_bwd_kernel(const float* __restrict__ dy, long lddy,
                                                              const float* __restrict__ x, long ldx,
                                                              const float* __restrict__ gamma,
@@ -145,7 +149,7 @@ __global__ __launch_bounds__(256) void ens_ln_act_bwd_kernel(const float* __rest
                                                              const float* __restrict__ rstd_in,
                                                              float* __restrict__ dx, long lddx,
                                                              float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                             int M, int N) {
+                                                             int M, int N, int act) {
   __shared__ float red[2][64 * NV];
   const int l = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int k = blockIdx.y;
@@ -177,7 +181,9 @@ __global__ __launch_bounds__(256) void ens_ln_act_bwd_kernel(const float* __rest
       dxh[v] = 0.f;
       if (c < N) {
         const float xhat = (x[r * ldx + c] - mean) * rstd;
-        const float dz = dy[r * lddy + c] * dsiluf_(xhat * g[v] + b[v]);
+        float dz = dy[r * lddy + c];
+        if constexpr (RT) dz *= dactf_(xhat * g[v] + b[v], act);
+        else dz *= dsiluf_(xhat * g[v] + b[v]);
         pg[v] += dz * xhat;
         pb[v] += dz;
         xh[v] = xhat;
@@ -473,19 +479,20 @@ extern "C" int dv3_ens_gemm_f32(int members, int transA, int transB, int M, int 
   return (int)hipGetLastError();
 }
 
-#define DV3_ENS_NV_DISPATCH(KERNEL, GRID, ...)                                                         \
+#define DV3_ENS_NV_DISPATCH(KERNEL, RT_, GRID, ...)                                                      \
   do {                                                                                                 \
-    if (N <= 64) hipLaunchKernelGGL((KERNEL<1>), GRID, dim3(256), 0, s, __VA_ARGS__);                  \
-    else if (N <= 128) hipLaunchKernelGGL((KERNEL<2>), GRID, dim3(256), 0, s, __VA_ARGS__);            \
-    else if (N <= 256) hipLaunchKernelGGL((KERNEL<4>), GRID, dim3(256), 0, s, __VA_ARGS__);            \
-    else if (N <= 512) hipLaunchKernelGGL((KERNEL<8>), GRID, dim3(256), 0, s, __VA_ARGS__);            \
-    else if (N <= 1024) hipLaunchKernelGGL((KERNEL<16>), GRID, dim3(256), 0, s, __VA_ARGS__);          \
-    else hipLaunchKernelGGL((KERNEL<32>), GRID, dim3(256), 0, s, __VA_ARGS__);                         \
+    if (N <= 64) hipLaunchKernelGGL((KERNEL<1, RT_>), GRID, dim3(256), 0, s, __VA_ARGS__);                  \
+    else if (N <= 128) hipLaunchKernelGGL((KERNEL<2, RT_>), GRID, dim3(256), 0, s, __VA_ARGS__);            \
+    else if (N <= 256) hipLaunchKernelGGL((KERNEL<4, RT_>), GRID, dim3(256), 0, s, __VA_ARGS__);            \
+    else if (N <= 512) hipLaunchKernelGGL((KERNEL<8, RT_>), GRID, dim3(256), 0, s, __VA_ARGS__);            \
+    else if (N <= 1024) hipLaunchKernelGGL((KERNEL<16, RT_>), GRID, dim3(256), 0, s, __VA_ARGS__);          \
+    else hipLaunchKernelGGL((KERNEL<32, RT_>), GRID, dim3(256), 0, s, __VA_ARGS__);                         \
   } while (0)
 
-extern "C" int dv3_ens_ln_act_fwd(const float* x, long ldx, const float* gamma, const float* beta, long strideG,
-                                  float* y, long ldy, float* mean, float* rstd, int members, int M, int N,
-                                  void* stream) {
+extern "C" int dv3_ens_ln_act_fwd_ex(const float* x, long ldx, const float* gamma, const float* beta, long strideG,
+                                     float* y, long ldy, float* mean, float* rstd, int members, int M, int N, int act,
+                                     void* stream) {
+  if (!dv3_act_ok(act)) return DV3_ERR_ARG;
   if (members <= 0 || M <= 0) return 0;
   if (!x || !gamma || !beta || !y || !mean || !rstd || N <= 0 || N > 2048 || ldx < N || ldy < N || strideG < 0)
     return DV3_ERR_ARG;
@@ -493,14 +500,26 @@ extern "C" int dv3_ens_ln_act_fwd(const float* x, long ldx, const float* gamma, 
   const long blocks = (R + 3) / 4;
   if (!fits_int(blocks)) return DV3_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-  DV3_ENS_NV_DISPATCH(ens_ln_act_fwd_kernel, dim3((unsigned)blocks), x, ldx, gamma, beta, strideG, y, ldy, mean,
-                      rstd, R, M, N);
+  if (act != DV3_ACT_SILU)  // (code 0 too: the SiLU instantiation has no switch)
+    DV3_ENS_NV_DISPATCH(ens_ln_act_fwd_kernel, true, dim3((unsigned)blocks), x, ldx, gamma, beta, strideG, y, ldy, mean,
+                        rstd, R, M, N, act);
+  else
+    DV3_ENS_NV_DISPATCH(ens_ln_act_fwd_kernel, false, dim3((unsigned)blocks), x, ldx, gamma, beta, strideG, y, ldy, mean,
+                        rstd, R, M, N, act);
   return (int)hipGetLastError();
 }
 
-extern "C" int dv3_ens_ln_act_bwd(const float* dy, long lddy, const float* x, long ldx, const float* gamma,
-                                  const float* beta, long strideG, const float* mean, const float* rstd, float* dx,
-                                  long lddx, float* dgamma, float* dbeta, int members, int M, int N, void* stream) {
+extern "C" int dv3_ens_ln_act_fwd(const float* x, long ldx, const float* gamma, const float* beta, long strideG,
+                                  float* y, long ldy, float* mean, float* rstd, int members, int M, int N,
+                                  void* stream) {
+  return dv3_ens_ln_act_fwd_ex(x, ldx, gamma, beta, strideG, y, ldy, mean, rstd, members, M, N, DV3_ACT_SILU, stream);
+}
+
+extern "C" int dv3_ens_ln_act_bwd_ex(const float* dy, long lddy, const float* x, long ldx, const float* gamma,
+                                     const float* beta, long strideG, const float* mean, const float* rstd, float* dx,
+                                     long lddx, float* dgamma, float* dbeta, int members, int M, int N, int act,
+                                     void* stream) {
+  if (!dv3_act_ok(act)) return DV3_ERR_ARG;
   if (members <= 0 || M <= 0) return 0;
   if (!dy || !x || !gamma || !beta || !mean || !rstd || !dx || N <= 0 || N > 2048 || lddy < N || ldx < N ||
       lddx < N || strideG < 0 || members > 65535 || (dgamma == nullptr) != (dbeta == nullptr))
@@ -508,9 +527,20 @@ extern "C" int dv3_ens_ln_act_bwd(const float* dy, long lddy, const float* x, lo
   int bx = (M + 3) / 4;
   if (bx > 64) bx = 64;
   hipStream_t s = (hipStream_t)stream;
-  DV3_ENS_NV_DISPATCH(ens_ln_act_bwd_kernel, dim3((unsigned)bx, (unsigned)members), dy, lddy, x, ldx, gamma, beta,
-                      strideG, mean, rstd, dx, lddx, dgamma, dbeta, M, N);
+  if (act != DV3_ACT_SILU)
+    DV3_ENS_NV_DISPATCH(ens_ln_act_bwd_kernel, true, dim3((unsigned)bx, (unsigned)members), dy, lddy, x, ldx, gamma, beta,
+                        strideG, mean, rstd, dx, lddx, dgamma, dbeta, M, N, act);
+  else
+    DV3_ENS_NV_DISPATCH(ens_ln_act_bwd_kernel, false, dim3((unsigned)bx, (unsigned)members), dy, lddy, x, ldx, gamma, beta,
+                        strideG, mean, rstd, dx, lddx, dgamma, dbeta, M, N, act);
   return (int)hipGetLastError();
+}
+
+extern "C" int dv3_ens_ln_act_bwd(const float* dy, long lddy, const float* x, long ldx, const float* gamma,
+                                  const float* beta, long strideG, const float* mean, const float* rstd, float* dx,
+                                  long lddx, float* dgamma, float* dbeta, int members, int M, int N, void* stream) {
+  return dv3_ens_ln_act_bwd_ex(dy, lddy, x, ldx, gamma, beta, strideG, mean, rstd, dx, lddx, dgamma, dbeta, members, M, N,
+                               DV3_ACT_SILU, stream);
 }
 
 extern "C" int dv3_ens_colsum(const float* x, long ldx, long strideX, float* out, long strideOut, int members, int M,

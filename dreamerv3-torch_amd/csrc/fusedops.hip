@@ -68,7 +68,7 @@ struct OLParams {
 // ONE batch of independent 16-byte loads (lane l owns columns 4*(l + 64 v) .. +3), the four partial rows meet in
 // LDS, and every wave then sums them in the same fixed order and normalises -- one memory round trip and one
 // barrier per row (a wave per row needed S / 8 dependent round trips at one wave per SIMD).
-template <int NV4, bool SMP = false>
+template <int NV4, bool SMP = false, bool RT = false>
 __global__ __launch_bounds__(SMP ? 1024 : 256) void onehot_linear_ln_vec_kernel(OLParams p) {
   __shared__ __attribute__((aligned(16))) float part[4][256 * NV4];
   __shared__ int sidx[64];
@@ -213,7 +213,8 @@ __global__ __launch_bounds__(SMP ? 1024 : 256) void onehot_linear_ln_vec_kernel(
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const float t = (acc[v][e] - mean) * rstd * g[e] + b[e];
-        z[e] = p.act ? siluf_(t) : t;
+        if constexpr (RT) z[e] = actf_(t, p.act);
+        else z[e] = p.act ? siluf_(t) : t;
       }
       *reinterpret_cast<f32x4u*>(p.y + r * p.ldy + 4 * (l + 64 * v)) = z;
     }
@@ -226,6 +227,7 @@ __global__ __launch_bounds__(SMP ? 1024 : 256) void onehot_linear_ln_vec_kernel(
 
 // any N (the tiny test configs, odd widths): a workgroup per row, columns strided over its 256 threads; the
 // pre-activation makes its passes through global memory (every thread re-reads only what it wrote)
+template <bool RT = false>
 __global__ __launch_bounds__(256) void onehot_linear_ln_generic_kernel(OLParams p) {
   __shared__ float red[4];
   __shared__ int sidx[64];
@@ -253,7 +255,8 @@ __global__ __launch_bounds__(256) void onehot_linear_ln_generic_kernel(OLParams 
     const float rstd = rsqrtf(block_sum_256(q, red) * inv_n + kLnEps);
     for (int c = tid; c < p.N; c += 256) {
       const float t = (p.pre[r * p.ldpre + c] - mean) * rstd * p.gamma[c] + p.beta[c];
-      p.y[r * p.ldy + c] = p.act ? siluf_(t) : t;
+      if constexpr (RT) p.y[r * p.ldy + c] = actf_(t, p.act);
+      else p.y[r * p.ldy + c] = p.act ? siluf_(t) : t;
     }
     if (tid == 0) {
       if (p.mean) p.mean[r] = mean;
@@ -291,13 +294,14 @@ struct AHParams {
   int U, A;
   float min_std, max_std, unimix;
   int onehot;
+  int act;  // activation code of the trunk's last layer (read by the runtime-code instantiation only)
 };
 
 // The heads are 2A (or A) dot products of length U per row.  Every wave of the chip walks the same weight rows, so
 // the loads of a batch of OB outputs are ALL issued before the first multiply (one memory round trip per batch, not
 // one per output), and wave w starts its batch at output w % OB so that the 1024 waves do not hit the same cache
 // lines at the same moment (from global memory in output order this took 26-36 us for 1024 rows).
-template <int NV>
+template <int NV, bool RT = false>
 __global__ __launch_bounds__(256) void actor_head_kernel(AHParams p) {
   __shared__ float hsh[4 * 16 * 65];
   __shared__ float hres[4 * 128];
@@ -357,7 +361,8 @@ __global__ __launch_bounds__(256) void actor_head_kernel(AHParams p) {
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
       const int c = l + 64 * v;
-      x[v] = c < p.U ? siluf_((x[v] - mean) * rstd * g[v] + b[v]) : 0.f;
+      if constexpr (RT) x[v] = c < p.U ? actf_((x[v] - mean) * rstd * g[v] + b[v], p.act) : 0.f;
+      else x[v] = c < p.U ? siluf_((x[v] - mean) * rstd * g[v] + b[v]) : 0.f;
       if (c < p.U) p.y[r * p.ldy + c] = x[v];
     }
     if (l == 0) {
@@ -568,7 +573,7 @@ extern "C" int dv3_onehot_linear_ln_fwd(const int* idx, int S, int D, const floa
                                         float* mean, float* rstd, long M, int N, int act, void* stream) {
   if (M <= 0) return 0;
   if (!idx || !WT || !pre || S <= 0 || S > 64 || D <= 0 || N <= 0 || A2 < 0 || (A2 > 0 && !x2) || ldw < N ||
-      ldpre < N || (base && ldbase < N))
+      ldpre < N || (base && ldbase < N) || !dv3_act_ok(act))
     return DV3_ERR_ARG;
   if (y && (!gamma || !beta || ldy < N)) return DV3_ERR_ARG;
   OLParams p{idx, S, D, x2, ldx2, A2, WT, ldw, base, ldbase, pre, ldpre, gamma, beta, y, ldy, mean, rstd, M, N, act};
@@ -577,14 +582,22 @@ extern "C" int dv3_onehot_linear_ln_fwd(const int* idx, int S, int D, const floa
                    (!y || ldy % 4 == 0);
   if (vec) {
     const dim3 grid(cap_grid(M, 1, 32768)), block(256);
-    switch (N / 256) {
+    if (dv3_act_rt(act)) switch (N / 256) {
+      case 1: hipLaunchKernelGGL((onehot_linear_ln_vec_kernel<1, false, true>), grid, block, 0, s, p); break;
+      case 2: hipLaunchKernelGGL((onehot_linear_ln_vec_kernel<2, false, true>), grid, block, 0, s, p); break;
+      case 3: hipLaunchKernelGGL((onehot_linear_ln_vec_kernel<3, false, true>), grid, block, 0, s, p); break;
+      default: hipLaunchKernelGGL((onehot_linear_ln_vec_kernel<4, false, true>), grid, block, 0, s, p); break;
+    }
+    else switch (N / 256) {
       case 1: hipLaunchKernelGGL((onehot_linear_ln_vec_kernel<1>), grid, block, 0, s, p); break;
       case 2: hipLaunchKernelGGL((onehot_linear_ln_vec_kernel<2>), grid, block, 0, s, p); break;
       case 3: hipLaunchKernelGGL((onehot_linear_ln_vec_kernel<3>), grid, block, 0, s, p); break;
       default: hipLaunchKernelGGL((onehot_linear_ln_vec_kernel<4>), grid, block, 0, s, p); break;
     }
+  } else if (dv3_act_rt(act)) {
+    hipLaunchKernelGGL(onehot_linear_ln_generic_kernel<true>, dim3(cap_grid(M, 1, 16384)), dim3(256), 0, s, p);
   } else {
-    hipLaunchKernelGGL(onehot_linear_ln_generic_kernel, dim3(cap_grid(M, 1, 16384)), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(onehot_linear_ln_generic_kernel<false>, dim3(cap_grid(M, 1, 16384)), dim3(256), 0, s, p);
   }
   return (int)hipGetLastError();
 }
@@ -606,6 +619,9 @@ extern "C" int dv3_onehot_sample_linear_ln_fwd(const float* logit, const float* 
       !beta || !y || S <= 0 || S > 32 || N <= 0 || (N % 256) != 0 || N > 1024 || A2 < 0 || (A2 > 0 && !x2) ||
       ldw < N || ldpre < N || ldy < N || (ldw % 4) || (ldpre % 4) || (ldy % 4))
     return DV3_ERR_ARG;
+  // codes 0 and 1 only: the 1024-thread sampling form has no registers to spare for the runtime-code activation (it
+  // would add scratch), so a layer with another activation takes dv3_onehot_sample_fwd_ex + dv3_onehot_linear_ln_fwd
+  if (!dv3_act_ok(act) || dv3_act_rt(act)) return DV3_ERR_ARG;
   if (!mode && !noise && !rng_state) return DV3_ERR_ARG;
   OLParams p{nullptr, S, 32, x2, ldx2, A2, WT, ldw, nullptr, 0, pre, ldpre, gamma, beta, y, ldy, mean, rstd, M, N, act,
              logit, noise, rng_state, rng_offset, onehot, idx, forced, flips, unimix, mode, next_first, init, init_idx,
@@ -621,13 +637,14 @@ extern "C" int dv3_onehot_sample_linear_ln_fwd(const float* logit, const float* 
   return (int)hipGetLastError();
 }
 
-extern "C" int dv3_actor_head_fwd(const float* pre, long ldpre, const float* gamma, const float* beta, float* y,
-                                  long ldy, float* mean, float* rstd, const float* Wm, const float* bm,
-                                  const float* Ws, const float* bs, float* out_m, float* out_s, const float* noise,
-                                  const unsigned long long* rng_state, unsigned long long rng_offset, float* eps_out,
-                                  float* action, float* entropy, int* act_idx, const int* forced,
-                                  unsigned int* flips, long M, int U, int A, float min_std, float max_std,
-                                  float unimix, int onehot, void* stream) {
+extern "C" int dv3_actor_head_fwd_ex(const float* pre, long ldpre, const float* gamma, const float* beta, float* y,
+                                     long ldy, float* mean, float* rstd, const float* Wm, const float* bm,
+                                     const float* Ws, const float* bs, float* out_m, float* out_s, const float* noise,
+                                     const unsigned long long* rng_state, unsigned long long rng_offset, float* eps_out,
+                                     float* action, float* entropy, int* act_idx, const int* forced,
+                                     unsigned int* flips, long M, int U, int A, float min_std, float max_std,
+                                     float unimix, int onehot, int act, void* stream) {
+  if (!dv3_act_ok(act)) return DV3_ERR_ARG;
   if (M <= 0) return 0;
   if (!pre || !gamma || !beta || !y || !Wm || !bm || !out_m || !action || U <= 0 || U > 1024 || A <= 0 || A > 64 ||
       ldpre < U || ldy < U)
@@ -636,14 +653,33 @@ extern "C" int dv3_actor_head_fwd(const float* pre, long ldpre, const float* gam
   if (onehot && Ws) return DV3_ERR_ARG;
   if (!noise && !rng_state) return DV3_ERR_ARG;
   AHParams p{pre, ldpre, gamma, beta, y, ldy, mean, rstd, Wm, bm, Ws, bs, out_m, out_s, noise, rng_state, rng_offset,
-             eps_out, action, entropy, act_idx, forced, flips, M, U, A, min_std, max_std, unimix, onehot};
+             eps_out, action, entropy, act_idx, forced, flips, M, U, A, min_std, max_std, unimix, onehot, act};
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid(cap_grid(M, 4, 4096)), block(256);
+  if (act != DV3_ACT_SILU) {  // (code 0 too: the SiLU instantiation has no switch)
+    if (U <= 64) hipLaunchKernelGGL((actor_head_kernel<1, true>), grid, block, 0, s, p);
+    else if (U <= 256) hipLaunchKernelGGL((actor_head_kernel<4, true>), grid, block, 0, s, p);
+    else if (U <= 512) hipLaunchKernelGGL((actor_head_kernel<8, true>), grid, block, 0, s, p);
+    else hipLaunchKernelGGL((actor_head_kernel<16, true>), grid, block, 0, s, p);
+    return (int)hipGetLastError();
+  }
   if (U <= 64) hipLaunchKernelGGL((actor_head_kernel<1>), grid, block, 0, s, p);
   else if (U <= 256) hipLaunchKernelGGL((actor_head_kernel<4>), grid, block, 0, s, p);
   else if (U <= 512) hipLaunchKernelGGL((actor_head_kernel<8>), grid, block, 0, s, p);
   else hipLaunchKernelGGL((actor_head_kernel<16>), grid, block, 0, s, p);
   return (int)hipGetLastError();
+}
+
+extern "C" int dv3_actor_head_fwd(const float* pre, long ldpre, const float* gamma, const float* beta, float* y,
+                                  long ldy, float* mean, float* rstd, const float* Wm, const float* bm,
+                                  const float* Ws, const float* bs, float* out_m, float* out_s, const float* noise,
+                                  const unsigned long long* rng_state, unsigned long long rng_offset, float* eps_out,
+                                  float* action, float* entropy, int* act_idx, const int* forced,
+                                  unsigned int* flips, long M, int U, int A, float min_std, float max_std,
+                                  float unimix, int onehot, void* stream) {
+  return dv3_actor_head_fwd_ex(pre, ldpre, gamma, beta, y, ldy, mean, rstd, Wm, bm, Ws, bs, out_m, out_s, noise, rng_state,
+                               rng_offset, eps_out, action, entropy, act_idx, forced, flips, M, U, A, min_std, max_std,
+                               unimix, onehot, DV3_ACT_SILU, stream);
 }
 
 extern "C" int dv3_transpose2d(const float* src, long lds, int R, int C, float* dst, long ldd, void* stream) {

@@ -22,7 +22,7 @@ __device__ __forceinline__ long act_addr(long r, int c, long ld, int N, int G) {
   return img * ((long)N * G) + (long)c * G + pix;
 }
 
-template <int LPR, int NV>
+template <int LPR, int NV, bool RT = false>
 __global__ __launch_bounds__(256) void ln_act_fwd_kernel(const float* __restrict__ x, long ldx,
                                                          const float* __restrict__ gamma,
                                                          const float* __restrict__ beta, float* __restrict__ y,
@@ -63,7 +63,8 @@ __global__ __launch_bounds__(256) void ln_act_fwd_kernel(const float* __restrict
       const int c = l + v * LPR;
       if (c < N) {
         float z = (xv[v] - mean) * rstd * g[v] + b[v];
-        if (act) z = siluf_(z);
+        if constexpr (RT) z = actf_(z, act);
+        else if (act) z = siluf_(z);
         y[act_addr(r, c, ldy, N, G)] = z;
       }
     }
@@ -75,7 +76,7 @@ __global__ __launch_bounds__(256) void ln_act_fwd_kernel(const float* __restrict
 }
 
 // dx = d(loss)/d(x) given dy = d(loss)/d(act(LN(x))).  dgamma/dbeta are ACCUMULATED (+=).
-template <int LPR, int NV>
+template <int LPR, int NV, bool RT = false>
 __global__ __launch_bounds__(256) void ln_act_bwd_kernel(const float* __restrict__ dy, long lddy,
                                                          const float* __restrict__ x, long ldx,
                                                          const float* __restrict__ gamma,
@@ -116,7 +117,8 @@ __global__ __launch_bounds__(256) void ln_act_bwd_kernel(const float* __restrict
       if (c < N) {
         const float xhat = (x[r * ldx + c] - mean) * rstd;
         float dz = dy[act_addr(r, c, lddy, N, G)];
-        if (act) dz *= dsiluf_(xhat * g[v] + b[v]);
+        if constexpr (RT) dz *= dactf_(xhat * g[v] + b[v], act);
+        else if (act) dz *= dsiluf_(xhat * g[v] + b[v]);
         pg[v] += dz * xhat;
         pb[v] += dz;
         xh[v] = xhat;
@@ -280,7 +282,7 @@ typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
 
 __device__ __forceinline__ float hsum(f4 a) { return (a.x + a.y) + (a.z + a.w); }
 
-template <int LPR, int NV>
+template <int LPR, int NV, bool RT = false>
 __global__ __launch_bounds__(256) void ln_act_fwd_vec_kernel(const float* __restrict__ x, long ldx,
                                                              const float* __restrict__ gamma,
                                                              const float* __restrict__ beta, float* __restrict__ y,
@@ -321,7 +323,9 @@ __global__ __launch_bounds__(256) void ln_act_fwd_vec_kernel(const float* __rest
       const int c = 4 * (l + LPR * v);
       if (c < N) {
         f4 z = (xv[v] - mean) * rstd * g[v] + b[v];
-        if (act) {
+        if constexpr (RT) {
+          z.x = actf_(z.x, act); z.y = actf_(z.y, act); z.z = actf_(z.z, act); z.w = actf_(z.w, act);
+        } else if (act) {
           z.x = siluf_(z.x); z.y = siluf_(z.y); z.z = siluf_(z.z); z.w = siluf_(z.w);
         }
         *reinterpret_cast<f4u*>(y + r * ldy + c) = z;
@@ -346,6 +350,7 @@ constexpr int kColBatch = 8;       // rows a wave loads together (branch-free, c
 // the partial column sums meet in LDS and one plain read-modify-write per column finishes the job.  No
 // atomics, no second launch, and the two roles run concurrently on different CUs (both only read inputs).
 // ------------------------------------------------------------------------------------------------
+template <bool RT>
 __device__ __forceinline__ void ln_bwd_cols(const float* __restrict__ dy, long lddy, const float* __restrict__ x, long ldx,
                                             const float* __restrict__ gamma, const float* __restrict__ beta,
                                             const float* __restrict__ mean_in, const float* __restrict__ rstd_in,
@@ -381,7 +386,8 @@ __device__ __forceinline__ void ln_bwd_cols(const float* __restrict__ dy, long l
     for (int i = 0; i < kColBatch; ++i) {
       const float xh = (xv[i] - mu[i]) * rs[i];
       float dz = (r0 + 4 * i < (int)R) ? dv[i] : 0.f;
-      if (act) dz *= dsiluf_(xh * g + b);
+      if constexpr (RT) dz *= dactf_(xh * g + b, act);
+      else if (act) dz *= dsiluf_(xh * g + b);
       pg += dz * xh;
       pb += dz;
     }
@@ -461,7 +467,7 @@ __device__ __forceinline__ void gru_bwd_cols(const float* __restrict__ dhn, long
   }
 }
 
-template <int LPR, int NV>
+template <int LPR, int NV, bool RT = false>
 __global__ __launch_bounds__(256) void ln_act_bwd_vec_kernel(const float* __restrict__ dy, long lddy,
                                                              const float* __restrict__ x, long ldx,
                                                              const float* __restrict__ gamma,
@@ -476,7 +482,7 @@ __global__ __launch_bounds__(256) void ln_act_bwd_vec_kernel(const float* __rest
   const int sub = threadIdx.x / LPR, l = threadIdx.x % LPR;
   __shared__ __attribute__((aligned(16))) float red[2][64 * kMaxV];
   if ((int)blockIdx.x >= row_blocks) {  // column role: owns 64 columns of d-gamma / d-beta
-    ln_bwd_cols(dy, lddy, x, ldx, gamma, beta, mean_in, rstd_in, dgamma, dbeta, R, N, act, (int)blockIdx.x - row_blocks,
+    ln_bwd_cols<RT>(dy, lddy, x, ldx, gamma, beta, mean_in, rstd_in, dgamma, dbeta, R, N, act, (int)blockIdx.x - row_blocks,
                 &red[0][0]);
     return;
   }
@@ -509,7 +515,10 @@ __global__ __launch_bounds__(256) void ln_act_bwd_vec_kernel(const float* __rest
       if (c < N) {
         const f4 xhat = (*reinterpret_cast<const f4u*>(x + r * ldx + c) - mean) * rstd;
         f4 dz = *reinterpret_cast<const f4u*>(dy + r * lddy + c);
-        if (act) {
+        if constexpr (RT) {
+          const f4 z = xhat * g[v] + b[v];
+          dz.x *= dactf_(z.x, act); dz.y *= dactf_(z.y, act); dz.z *= dactf_(z.z, act); dz.w *= dactf_(z.w, act);
+        } else if (act) {
           const f4 z = xhat * g[v] + b[v];
           dz.x *= dsiluf_(z.x); dz.y *= dsiluf_(z.y); dz.z *= dsiluf_(z.z); dz.w *= dsiluf_(z.w);
         }
@@ -963,23 +972,23 @@ __global__ __launch_bounds__(256) void gru_bwd_wide_kernel(const float* __restri
   }
 }
 
-template <int LPR, int NV>
+template <int LPR, int NV, bool RT = false>
 static void launch_ln_fwd(const float* x, long ldx, const float* g, const float* b, float* y, long ldy, float* mean,
                           float* rstd, long R, int N, int act, int G, hipStream_t s) {
   const long rpb = 256 / LPR;
   long blocks = (R + rpb - 1) / rpb;
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL((ln_act_fwd_kernel<LPR, NV>), dim3((unsigned)blocks), dim3(256), 0, s, x, ldx, g, b, y, ldy, mean,
+  hipLaunchKernelGGL((ln_act_fwd_kernel<LPR, NV, RT>), dim3((unsigned)blocks), dim3(256), 0, s, x, ldx, g, b, y, ldy, mean,
                      rstd, R, N, act, G);
 }
-template <int LPR, int NV>
+template <int LPR, int NV, bool RT = false>
 static void launch_ln_bwd(const float* dy, long lddy, const float* x, long ldx, const float* g, const float* b,
                           const float* mean, const float* rstd, float* dx, long lddx, float* dg, float* db, long R,
                           int N, int act, int G, int acc, hipStream_t s) {
   const long rpb = 256 / LPR;
   long blocks = (R + rpb - 1) / rpb;
   if (blocks > 512) blocks = 512;  // fewer blocks -> fewer dgamma/dbeta atomics
-  hipLaunchKernelGGL((ln_act_bwd_kernel<LPR, NV>), dim3((unsigned)blocks), dim3(256), 0, s, dy, lddy, x, ldx, g, b, mean,
+  hipLaunchKernelGGL((ln_act_bwd_kernel<LPR, NV, RT>), dim3((unsigned)blocks), dim3(256), 0, s, dy, lddy, x, ldx, g, b, mean,
                      rstd, dx, lddx, dg, db, R, N, act, G, acc);
 }
 static int pick_lpr(int N) {
@@ -989,21 +998,21 @@ static int pick_lpr(int N) {
 }
 // dispatch on (lanes per row, elements per lane): sub-wave groups for short rows (conv channels),
 // a full wave with 1..32 cached elements per lane for long ones
-#define DV3_LN_DISPATCH(FN, ...)                                   \
+#define DV3_LN_DISPATCH(FN, RT_, ...)                                 \
   do {                                                             \
     const int lpr_ = pick_lpr(N);                                  \
-    if (lpr_ == 4) FN<4, 1>(__VA_ARGS__);                          \
-    else if (lpr_ == 8) FN<8, 1>(__VA_ARGS__);                     \
-    else if (lpr_ == 16) FN<16, 1>(__VA_ARGS__);                   \
-    else if (lpr_ == 32) FN<32, 1>(__VA_ARGS__);                   \
+    if (lpr_ == 4) FN<4, 1, RT_>(__VA_ARGS__);                          \
+    else if (lpr_ == 8) FN<8, 1, RT_>(__VA_ARGS__);                     \
+    else if (lpr_ == 16) FN<16, 1, RT_>(__VA_ARGS__);                   \
+    else if (lpr_ == 32) FN<32, 1, RT_>(__VA_ARGS__);                   \
     else {                                                         \
       const int nv_ = (N + 63) / 64;                               \
-      if (nv_ <= 1) FN<64, 1>(__VA_ARGS__);                        \
-      else if (nv_ <= 2) FN<64, 2>(__VA_ARGS__);                   \
-      else if (nv_ <= 4) FN<64, 4>(__VA_ARGS__);                   \
-      else if (nv_ <= 8) FN<64, 8>(__VA_ARGS__);                   \
-      else if (nv_ <= 16) FN<64, 16>(__VA_ARGS__);                 \
-      else FN<64, 32>(__VA_ARGS__);                                \
+      if (nv_ <= 1) FN<64, 1, RT_>(__VA_ARGS__);                        \
+      else if (nv_ <= 2) FN<64, 2, RT_>(__VA_ARGS__);                   \
+      else if (nv_ <= 4) FN<64, 4, RT_>(__VA_ARGS__);                   \
+      else if (nv_ <= 8) FN<64, 8, RT_>(__VA_ARGS__);                   \
+      else if (nv_ <= 16) FN<64, 16, RT_>(__VA_ARGS__);                 \
+      else FN<64, 32, RT_>(__VA_ARGS__);                                \
     }                                                              \
   } while (0)
 
@@ -1020,7 +1029,7 @@ static bool vec_shape(int N, int& lpr, int& nv) {
   nv = (chunks + lpr - 1) / lpr;
   return nv <= 8;
 }
-#define DV3_LNV_DISPATCH(KERNEL, GRIDCAP, EXTRA, ...)                                                     \
+#define DV3_LNV_DISPATCH(KERNEL, RT_, GRIDCAP, EXTRA, ...)                                                     \
   do {                                                                                               \
     int lpr_, nv_;                                                                                   \
     vec_shape(N, lpr_, nv_);                                                                         \
@@ -1028,29 +1037,31 @@ static bool vec_shape(int N, int& lpr, int& nv) {
     long blocks_ = (R + rpb_ - 1) / rpb_;                                                            \
     if (blocks_ > (GRIDCAP)) blocks_ = (GRIDCAP);                                                    \
     const dim3 g_((unsigned)(blocks_ + (EXTRA))), b_(256);                                           \
-    if (lpr_ == 4) hipLaunchKernelGGL((KERNEL<4, 1>), g_, b_, 0, s, __VA_ARGS__);                    \
-    else if (lpr_ == 8) hipLaunchKernelGGL((KERNEL<8, 1>), g_, b_, 0, s, __VA_ARGS__);               \
-    else if (lpr_ == 16) hipLaunchKernelGGL((KERNEL<16, 1>), g_, b_, 0, s, __VA_ARGS__);             \
-    else if (lpr_ == 32) hipLaunchKernelGGL((KERNEL<32, 1>), g_, b_, 0, s, __VA_ARGS__);             \
-    else if (nv_ <= 1) hipLaunchKernelGGL((KERNEL<64, 1>), g_, b_, 0, s, __VA_ARGS__);               \
-    else if (nv_ <= 2) hipLaunchKernelGGL((KERNEL<64, 2>), g_, b_, 0, s, __VA_ARGS__);               \
-    else if (nv_ <= 4) hipLaunchKernelGGL((KERNEL<64, 4>), g_, b_, 0, s, __VA_ARGS__);               \
-    else hipLaunchKernelGGL((KERNEL<64, 8>), g_, b_, 0, s, __VA_ARGS__);                             \
+    if (lpr_ == 4) hipLaunchKernelGGL((KERNEL<4, 1, RT_>), g_, b_, 0, s, __VA_ARGS__);                    \
+    else if (lpr_ == 8) hipLaunchKernelGGL((KERNEL<8, 1, RT_>), g_, b_, 0, s, __VA_ARGS__);               \
+    else if (lpr_ == 16) hipLaunchKernelGGL((KERNEL<16, 1, RT_>), g_, b_, 0, s, __VA_ARGS__);             \
+    else if (lpr_ == 32) hipLaunchKernelGGL((KERNEL<32, 1, RT_>), g_, b_, 0, s, __VA_ARGS__);             \
+    else if (nv_ <= 1) hipLaunchKernelGGL((KERNEL<64, 1, RT_>), g_, b_, 0, s, __VA_ARGS__);               \
+    else if (nv_ <= 2) hipLaunchKernelGGL((KERNEL<64, 2, RT_>), g_, b_, 0, s, __VA_ARGS__);               \
+    else if (nv_ <= 4) hipLaunchKernelGGL((KERNEL<64, 4, RT_>), g_, b_, 0, s, __VA_ARGS__);               \
+    else hipLaunchKernelGGL((KERNEL<64, 8, RT_>), g_, b_, 0, s, __VA_ARGS__);                             \
   } while (0)
 
 extern "C" int dv3_ln_act_fwd(const float* x, long ldx, const float* gamma, const float* beta, float* y, long ldy,
                               float* mean, float* rstd, long R, int N, int act, int chw_group, void* stream) {
   if (R <= 0) return 0;
-  if (N <= 0 || N > 64 * kMaxV || !x || !y || !gamma || !beta) return DV3_ERR_ARG;
+  if (N <= 0 || N > 64 * kMaxV || !x || !y || !gamma || !beta || !dv3_act_ok(act)) return DV3_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   {
     int lpr0, nv0;
     if (chw_group <= 0 && vec_shape(N, lpr0, nv0)) {
-      DV3_LNV_DISPATCH(ln_act_fwd_vec_kernel, 8192, 0, x, ldx, gamma, beta, y, ldy, mean, rstd, R, N, act);
+      if (dv3_act_rt(act)) DV3_LNV_DISPATCH(ln_act_fwd_vec_kernel, true, 8192, 0, x, ldx, gamma, beta, y, ldy, mean, rstd, R, N, act);
+      else DV3_LNV_DISPATCH(ln_act_fwd_vec_kernel, false, 8192, 0, x, ldx, gamma, beta, y, ldy, mean, rstd, R, N, act);
       return (int)hipGetLastError();
     }
   }
-  DV3_LN_DISPATCH(launch_ln_fwd, x, ldx, gamma, beta, y, ldy, mean, rstd, R, N, act, chw_group, s);
+  if (dv3_act_rt(act)) DV3_LN_DISPATCH(launch_ln_fwd, true, x, ldx, gamma, beta, y, ldy, mean, rstd, R, N, act, chw_group, s);
+  else DV3_LN_DISPATCH(launch_ln_fwd, false, x, ldx, gamma, beta, y, ldy, mean, rstd, R, N, act, chw_group, s);
   return (int)hipGetLastError();
 }
 
@@ -1061,7 +1072,8 @@ static int ln_act_bwd_impl(const float* dy, long lddy, const float* x, long ldx,
                            long R, int N, int act, int chw_group, int accumulate_dx, float* ws, long ws_floats,
                            void* stream) {
   if (R <= 0) return 0;
-  if (N <= 0 || N > 64 * kMaxV || !x || !dy || !dx || !gamma || !beta || !mean || !rstd) return DV3_ERR_ARG;
+  if (N <= 0 || N > 64 * kMaxV || !x || !dy || !dx || !gamma || !beta || !mean || !rstd || !dv3_act_ok(act))
+    return DV3_ERR_ARG;
   if ((dgamma == nullptr) != (dbeta == nullptr)) return DV3_ERR_ARG;
   if (ws && ws_floats < kLnPartRows * 2 * N) return DV3_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
@@ -1079,8 +1091,12 @@ static int ln_act_bwd_impl(const float* dy, long lddy, const float* x, long ldx,
       const int col_blocks = col_role ? ((N + 63) / 64) * (int)((R + kColRoleRows - 1) / kColRoleRows) : 0;
       float* part = two_stage ? ws : nullptr;
       int nb = 0;
-      DV3_LNV_DISPATCH(ln_act_bwd_vec_kernel, cap, col_blocks, dy, lddy, x, ldx, gamma, beta, mean, rstd, dx, lddx, dgamma,
-                       dbeta, R, N, act, accumulate_dx, (nb = (int)blocks_), part);
+      if (dv3_act_rt(act))
+        DV3_LNV_DISPATCH(ln_act_bwd_vec_kernel, true, cap, col_blocks, dy, lddy, x, ldx, gamma, beta, mean, rstd, dx, lddx,
+                         dgamma, dbeta, R, N, act, accumulate_dx, (nb = (int)blocks_), part);
+      else
+        DV3_LNV_DISPATCH(ln_act_bwd_vec_kernel, false, cap, col_blocks, dy, lddy, x, ldx, gamma, beta, mean, rstd, dx, lddx,
+                         dgamma, dbeta, R, N, act, accumulate_dx, (nb = (int)blocks_), part);
       if (two_stage) {
         const int slices = nb >= 256 ? kFoldSlices : 1;
         hipLaunchKernelGGL(ln_fold_partials_kernel, dim3((2 * N + 63) / 64, slices), dim3(256), 0, s, part, nb, N, dgamma,
@@ -1089,8 +1105,12 @@ static int ln_act_bwd_impl(const float* dy, long lddy, const float* x, long ldx,
       return (int)hipGetLastError();
     }
   }
-  DV3_LN_DISPATCH(launch_ln_bwd, dy, lddy, x, ldx, gamma, beta, mean, rstd, dx, lddx, dgamma, dbeta, R, N, act, chw_group,
-                  accumulate_dx, s);
+  if (dv3_act_rt(act))
+    DV3_LN_DISPATCH(launch_ln_bwd, true, dy, lddy, x, ldx, gamma, beta, mean, rstd, dx, lddx, dgamma, dbeta, R, N, act,
+                    chw_group, accumulate_dx, s);
+  else
+    DV3_LN_DISPATCH(launch_ln_bwd, false, dy, lddy, x, ldx, gamma, beta, mean, rstd, dx, lddx, dgamma, dbeta, R, N, act,
+                    chw_group, accumulate_dx, s);
   return (int)hipGetLastError();
 }
 

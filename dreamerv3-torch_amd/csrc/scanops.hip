@@ -65,11 +65,12 @@ struct ScanLnParams {
   float* C;  // [M, N]
   long ldc;
   int M, K, N, accumulate;
+  int act;  // activation code (read by the runtime-code instantiation only)
 };
 
 // C[M,N] (+)= SiLU(LN(x)) W^T + bias   (ln_act_fwd_vec_kernel<64, NV> + gemm_skinny_kernel<true, 1, .>)
 // grid (N / 16, 1, ceil(M / 16)), 512 threads.  K = 256 NV.
-template <int NV>
+template <int NV, bool RT = false>
 __global__ __launch_bounds__(64 * kScanWaves) void scan_ln_gemm_kernel(ScanLnParams p) {
   constexpr int PER = 2 * NV;
   __shared__ float red[kScanWaves][256];
@@ -136,7 +137,11 @@ __global__ __launch_bounds__(64 * kScanWaves) void scan_ln_gemm_kernel(ScanLnPar
   for (int u = 0; u < PER; ++u) {
     const int k = ((cb + u) << 4) + 4 * q;
     f32x4 z = (xa[u] - mean) * rstd * *reinterpret_cast<const f32x4*>(&sgb[0][k]) + *reinterpret_cast<const f32x4*>(&sgb[1][k]);
-    z.x = siluf_(z.x); z.y = siluf_(z.y); z.z = siluf_(z.z); z.w = siluf_(z.w);
+    if constexpr (RT) {
+      z.x = actf_(z.x, p.act); z.y = actf_(z.y, p.act); z.z = actf_(z.z, p.act); z.w = actf_(z.w, p.act);
+    } else {
+      z.x = siluf_(z.x); z.y = siluf_(z.y); z.z = siluf_(z.z); z.w = siluf_(z.w);
+    }
     if (writer) *reinterpret_cast<f32x4u*>(p.y + (long)row * p.ldy + k) = z;
 #pragma unroll
     for (int g = 0; g < 4; ++g) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(z[g] * amask, b[u][g] * bmask, acc, 0, 0, 0);
@@ -171,12 +176,13 @@ struct ScanLnBwdParams {
 
 // xhat = (x - mean) rstd and jac = SiLU'(xhat gamma + beta) for every row of a LayerNorm + SiLU layer: the factors of
 // its backward pass that depend on forward data only (float4 per thread; K % 4 == 0).
+template <bool RT = false>
 __global__ __launch_bounds__(256) void scan_ln_factors_kernel(const float* __restrict__ x, long ldx,
                                                               const float* __restrict__ gamma,
                                                               const float* __restrict__ beta,
                                                               const float* __restrict__ mean,
                                                               const float* __restrict__ rstd, float* __restrict__ xhat,
-                                                              float* __restrict__ jac, long R, int K) {
+                                                              float* __restrict__ jac, long R, int K, int act) {
   const long total = R * (K / 4);
   for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
     const long r = e / (K / 4);
@@ -184,7 +190,11 @@ __global__ __launch_bounds__(256) void scan_ln_factors_kernel(const float* __res
     const f32x4 xh = (*reinterpret_cast<const f32x4u*>(x + r * ldx + c) - mean[r]) * rstd[r];
     const f32x4 z = xh * *reinterpret_cast<const f32x4u*>(gamma + c) + *reinterpret_cast<const f32x4u*>(beta + c);
     f32x4 j;
-    j.x = dsiluf_(z.x); j.y = dsiluf_(z.y); j.z = dsiluf_(z.z); j.w = dsiluf_(z.w);
+    if constexpr (RT) {
+      j.x = dactf_(z.x, act); j.y = dactf_(z.y, act); j.z = dactf_(z.z, act); j.w = dactf_(z.w, act);
+    } else {
+      j.x = dsiluf_(z.x); j.y = dsiluf_(z.y); j.z = dsiluf_(z.z); j.w = dsiluf_(z.w);
+    }
     *reinterpret_cast<f32x4u*>(xhat + r * K + c) = xh;
     *reinterpret_cast<f32x4u*>(jac + r * K + c) = j;
   }
@@ -596,34 +606,57 @@ __global__ __launch_bounds__(64 * kScanWaves) void scan_carry_st_gemm_kernel(Sca
 
 using namespace dv3;
 
-extern "C" int dv3_scan_ln_gemm_fwd(const float* x, long ldx, const float* gamma, const float* beta, float* y, long ldy,
-                                    float* mean, float* rstd, const float* W, long ldw, const float* bias, float* C,
-                                    long ldc, int M, int K, int N, int accumulate, void* stream) {
+extern "C" int dv3_scan_ln_gemm_fwd_ex(const float* x, long ldx, const float* gamma, const float* beta, float* y,
+                                       long ldy, float* mean, float* rstd, const float* W, long ldw, const float* bias,
+                                       float* C, long ldc, int M, int K, int N, int accumulate, int act, void* stream) {
+  if (!dv3_act_ok(act)) return DV3_ERR_ARG;
   if (M <= 0 || N <= 0) return 0;
   if (!x || !gamma || !beta || !W || !C) return DV3_ERR_ARG;
   if (K <= 0 || K % 256 != 0 || K > 1024 || N % 16 != 0) return DV3_ERR_ARG;
   if (ldx < K || ldw < K || ldc < N || (y && ldy < K)) return DV3_ERR_ARG;
-  ScanLnParams p{x, ldx, gamma, beta, y, ldy, mean, rstd, W, ldw, bias, C, ldc, M, K, N, accumulate};
+  ScanLnParams p{x, ldx, gamma, beta, y, ldy, mean, rstd, W, ldw, bias, C, ldc, M, K, N, accumulate, act};
   const dim3 grid(N / 16, 1, (M + 15) / 16), block(64 * kScanWaves);
   hipStream_t s = (hipStream_t)stream;
-  switch (K / 256) {
+  if (K / 256 != 1 && K / 256 != 2 && K / 256 != 4) return DV3_ERR_ARG;
+  if (act != DV3_ACT_SILU) switch (K / 256) {  // (code 0 too: the SiLU instantiation has no switch)
+    case 1: hipLaunchKernelGGL((scan_ln_gemm_kernel<1, true>), grid, block, 0, s, p); break;
+    case 2: hipLaunchKernelGGL((scan_ln_gemm_kernel<2, true>), grid, block, 0, s, p); break;
+    default: hipLaunchKernelGGL((scan_ln_gemm_kernel<4, true>), grid, block, 0, s, p); break;
+  }
+  else switch (K / 256) {
     case 1: hipLaunchKernelGGL((scan_ln_gemm_kernel<1>), grid, block, 0, s, p); break;
     case 2: hipLaunchKernelGGL((scan_ln_gemm_kernel<2>), grid, block, 0, s, p); break;
-    case 4: hipLaunchKernelGGL((scan_ln_gemm_kernel<4>), grid, block, 0, s, p); break;
-    default: return DV3_ERR_ARG;
+    default: hipLaunchKernelGGL((scan_ln_gemm_kernel<4>), grid, block, 0, s, p); break;
   }
+  return (int)hipGetLastError();
+}
+
+extern "C" int dv3_scan_ln_gemm_fwd(const float* x, long ldx, const float* gamma, const float* beta, float* y, long ldy,
+                                    float* mean, float* rstd, const float* W, long ldw, const float* bias, float* C,
+                                    long ldc, int M, int K, int N, int accumulate, void* stream) {
+  return dv3_scan_ln_gemm_fwd_ex(x, ldx, gamma, beta, y, ldy, mean, rstd, W, ldw, bias, C, ldc, M, K, N, accumulate,
+                                 DV3_ACT_SILU, stream);
+}
+
+extern "C" int dv3_scan_ln_factors_ex(const float* x, long ldx, const float* gamma, const float* beta, const float* mean,
+                                      const float* rstd, float* xhat, float* jac, long R, int K, int act, void* stream) {
+  if (!dv3_act_ok(act)) return DV3_ERR_ARG;
+  if (R <= 0) return 0;
+  if (!x || !gamma || !beta || !mean || !rstd || !xhat || !jac || K <= 0 || K % 4 != 0 || ldx < K) return DV3_ERR_ARG;
+  long blocks = (R * (K / 4) + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  if (act != DV3_ACT_SILU)
+    hipLaunchKernelGGL(scan_ln_factors_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, ldx,
+                       gamma, beta, mean, rstd, xhat, jac, R, K, act);
+  else
+    hipLaunchKernelGGL(scan_ln_factors_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, ldx,
+                       gamma, beta, mean, rstd, xhat, jac, R, K, act);
   return (int)hipGetLastError();
 }
 
 extern "C" int dv3_scan_ln_factors(const float* x, long ldx, const float* gamma, const float* beta, const float* mean,
                                    const float* rstd, float* xhat, float* jac, long R, int K, void* stream) {
-  if (R <= 0) return 0;
-  if (!x || !gamma || !beta || !mean || !rstd || !xhat || !jac || K <= 0 || K % 4 != 0 || ldx < K) return DV3_ERR_ARG;
-  long blocks = (R * (K / 4) + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(scan_ln_factors_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, ldx, gamma, beta,
-                     mean, rstd, xhat, jac, R, K);
-  return (int)hipGetLastError();
+  return dv3_scan_ln_factors_ex(x, ldx, gamma, beta, mean, rstd, xhat, jac, R, K, DV3_ACT_SILU, stream);
 }
 
 extern "C" int dv3_scan_lnbwd_gemm(const float* dy, long lddy, const float* xhat, const float* jac, const float* gamma,

@@ -98,16 +98,16 @@ class LinearFn(Function):
 
 
 class TrunkFn(Function):
-    """n x [Linear(no bias) -> LayerNorm(eps 1e-3) -> SiLU] (networks.MLP.layers, networks.py:624-635; the RSSM's
+    """n x [Linear(no bias) -> LayerNorm(eps 1e-3) -> act] (networks.MLP.layers, networks.py:624-635; the RSSM's
     `_img_in_layers` / `_img_out_layers` / `_obs_out_layers`, networks.py:44-78) through engine.MLPEngine.
-    params = (W0, g0, b0, W1, g1, b1, ...)."""
+    act: the layers' activation code (ops.ACT_CODES); params = (W0, g0, b0, W1, g1, b1, ...)."""
 
     @staticmethod
-    def forward(ctx, x, *params):
+    def forward(ctx, x, act, *params):
         n = len(params) // 3
         x2 = _rows(x)
-        layers = [E.PDenseLN(_shadow(params[3 * i]), _shadow(params[3 * i + 1]), _shadow(params[3 * i + 2]))
-                  for i in range(n)]
+        layers = [E.PDenseLN(_shadow(params[3 * i]), _shadow(params[3 * i + 1]), _shadow(params[3 * i + 2]),
+                             ops.act_code(act)) for i in range(n)]
         eng = E.MLPEngine("ag", E.PMLP(layers), E.Workspace(x.device))
         h, _, _ = eng.forward(x2)
         ctx.eng, ctx.x2, ctx.layers = eng, x2, layers
@@ -120,13 +120,13 @@ class TrunkFn(Function):
         eng, x2 = ctx.eng, ctx.x2
         R = x2.shape[0]
         dx = torch.empty_like(x2) if ctx.needs_input_grad[0] else None
-        eng.backward(x2, None, slice(0, R), dh=_c(dh.reshape(R, -1)), wgrad=any(ctx.needs_input_grad[1:]), dx1=dx)
+        eng.backward(x2, None, slice(0, R), dh=_c(dh.reshape(R, -1)), wgrad=any(ctx.needs_input_grad[2:]), dx1=dx)
         grads: List[Optional[torch.Tensor]] = []
         for i, L in enumerate(ctx.layers):
             for j, t in enumerate((L.W, L.g, L.b)):
-                grads.append(t.grad if ctx.needs_input_grad[1 + 3 * i + j] else None)
+                grads.append(t.grad if ctx.needs_input_grad[2 + 3 * i + j] else None)
         ctx.eng = None
-        return (None if dx is None else dx.view(ctx.lead + (x2.shape[1],)),) + tuple(grads)
+        return (None if dx is None else dx.view(ctx.lead + (x2.shape[1],)), None) + tuple(grads)
 
 
 class GRUFn(Function):
@@ -344,16 +344,17 @@ def rssm_param_list(P: E.PRSSM) -> List[torch.Tensor]:
             P.img_out.b, P.obs_out.W, P.obs_out.g, P.obs_out.b, P.ims.W, P.ims.b, P.obs.W, P.obs.b]
 
 
-def _rssm_shadow(params: Sequence[torch.Tensor]) -> E.PRSSM:
+def _rssm_shadow(params: Sequence[torch.Tensor], act: int = 1) -> E.PRSSM:
     s = [_shadow(p) for p in params]
-    return E.PRSSM(s[0], E.PDenseLN(*s[1:4]), E.PDenseLN(*s[4:7]), E.PDenseLN(*s[7:10]), E.PDenseLN(*s[10:13]),
-                   E.PLin(*s[13:15]), E.PLin(*s[15:17]))
+    return E.PRSSM(s[0], E.PDenseLN(*s[1:4], act), E.PDenseLN(*s[4:7]), E.PDenseLN(*s[7:10], act),
+                   E.PDenseLN(*s[10:13], act), E.PLin(*s[13:15]), E.PLin(*s[15:17]))
 
 
 def _observe_forward(ctx, embed_tm, action_tm, first_tm, q_prior, q_post, rng, dims, params, keys):
     """Forward of both observe nodes: a private engine over shadow parameters runs observe_fwd, ctx keeps it for the
     backward, and the outputs are clones of the engine's buffers `keys`."""
-    P = _rssm_shadow(params)
+    dims = dict(dims)
+    P = _rssm_shadow(params, ops.act_code(dims.pop("act", True)))  # (dims["act"]: the three dense blocks' activation)
     eng = E.RSSMEngine(P, E.Workspace(embed_tm.device), **dims)
     f32 = lambda x: x.detach().to(F32).contiguous()
     out = eng.observe_fwd(f32(embed_tm), f32(action_tm), f32(first_tm), q_prior=q_prior, q_post=q_post, rng=rng)
@@ -426,13 +427,13 @@ class ObserveGaussFn(Function):
 # conv stacks
 # ---------------------------------------------------------------------------------------------
 class ConvEncoderFn(Function):
-    """networks.ConvEncoder.forward (networks.py:486-496) on x = image - 0.5 [N,H,W,C]; params = (W, g, b) per layer.
-    The image itself gets no gradient (it is data for every caller)."""
+    """networks.ConvEncoder.forward (networks.py:486-496) on x = image - 0.5 [N,H,W,C]; act: the layers' activation
+    code; params = (W, g, b) per layer.  The image itself gets no gradient (it is data for every caller)."""
 
     @staticmethod
-    def forward(ctx, x, size, *params):
-        layers = [E.PConvLayer(_shadow(params[3 * i]), _shadow(params[3 * i + 1]), _shadow(params[3 * i + 2]))
-                  for i in range(len(params) // 3)]
+    def forward(ctx, x, size, act, *params):
+        layers = [E.PConvLayer(_shadow(params[3 * i]), _shadow(params[3 * i + 1]), _shadow(params[3 * i + 2]),
+                               act=ops.act_code(act)) for i in range(len(params) // 3)]
         eng = E.ConvEncoderEngine(layers, E.Workspace(x.device), size=size)
         emb = eng.forward(x_f32=x.detach().to(F32).contiguous(), keep=True)
         ctx.eng, ctx.layers = eng, layers
@@ -445,22 +446,22 @@ class ConvEncoderFn(Function):
         grads = []
         for i, L in enumerate(ctx.layers):
             for j, t in enumerate((L.W, L.g, L.b)):
-                grads.append(t.grad if ctx.needs_input_grad[2 + 3 * i + j] else None)
+                grads.append(t.grad if ctx.needs_input_grad[3 + 3 * i + j] else None)
         ctx.eng = None
-        return (None, None) + tuple(grads)
+        return (None, None, None) + tuple(grads)
 
 
 class ConvDecoderFn(Function):
     """networks.ConvDecoder.forward (networks.py:568-585): feat [R,F] -> mean image [R,64,64,3] (+0.5).
-    params = (lin.W, lin.b, W0, g0, b0, ..., W_last, bias_last)."""
+    act: the layers' activation code; params = (lin.W, lin.b, W0, g0, b0, ..., W_last, bias_last)."""
 
     @staticmethod
-    def forward(ctx, feat, minres, *params):
+    def forward(ctx, feat, minres, act, *params):
         lin = E.PLin(_shadow(params[0]), _shadow(params[1]))
         rest = params[2:]
         n_ln = (len(rest) - 2) // 3
-        layers = [E.PConvLayer(_shadow(rest[3 * i]), _shadow(rest[3 * i + 1]), _shadow(rest[3 * i + 2]))
-                  for i in range(n_ln)]
+        layers = [E.PConvLayer(_shadow(rest[3 * i]), _shadow(rest[3 * i + 1]), _shadow(rest[3 * i + 2]),
+                               act=ops.act_code(act)) for i in range(n_ln)]
         layers.append(E.PConvLayer(_shadow(rest[-2]), None, None, _shadow(rest[-1])))
         eng = E.ConvDecoderEngine(lin, layers, E.Workspace(feat.device), minres=minres)
         x = _rows(feat)
@@ -482,9 +483,9 @@ class ConvDecoderFn(Function):
         for L in ctx.layers[:-1]:
             flat += [L.W, L.g, L.b]
         flat += [ctx.layers[-1].W, ctx.layers[-1].bias]
-        grads = [t.grad if ctx.needs_input_grad[2 + i] else None for i, t in enumerate(flat)]
+        grads = [t.grad if ctx.needs_input_grad[3 + i] else None for i, t in enumerate(flat)]
         ctx.eng = None
-        return (torch.cat([dx1, dx2], 1) if ctx.needs_input_grad[0] else None, None) + tuple(grads)
+        return (torch.cat([dx1, dx2], 1) if ctx.needs_input_grad[0] else None, None, None) + tuple(grads)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -433,6 +433,7 @@ class PDenseLN:
     W: torch.Tensor
     g: torch.Tensor
     b: torch.Tensor
+    act: int = 1  # activation code behind the LayerNorm (ops.ACT_CODES; 1 = SiLU)
 
 
 @dataclass
@@ -466,12 +467,12 @@ def v2(t: torch.Tensor, cols: int) -> torch.Tensor:
 # ---------------------------------------------------------------------------------------------
 def dense_ln_fwd(L: PDenseLN, x1, x2, pre, mean, rstd, y, *, accumulate_pre=False):
     ops.gemm(x1, L.W, pre, A2=x2, accumulate=accumulate_pre)
-    ops.ln_act_fwd(pre, L.g, L.b, y, mean, rstd, act=True)
+    ops.ln_act_fwd(pre, L.g, L.b, y, mean, rstd, act=L.act)
 
 
 def dense_ln_bwd_pre(L: PDenseLN, dy, pre, mean, rstd, dpre, *, wgrad: bool):
     ops.ln_act_bwd(dy, pre, L.g, L.b, mean, rstd, dpre, _g(L.g) if wgrad else None, _g(L.b) if wgrad else None,
-                   act=True)
+                   act=L.act)
 
 
 def lin_wgrad(W, dY, x1, x2=None):
@@ -549,7 +550,7 @@ class MLPEngine:
                     ops.onehot_linear_ln(idx, D, wt, pre[rs], base=base)
                 else:
                     ops.onehot_linear_ln(idx, D, wt, pre[rs], base=base, gamma=L.g, beta=L.b, y=y[rs], mean=mean[rs],
-                                         rstd=rstd[rs])
+                                         rstd=rstd[rs], act=L.act)
             elif last_fused:
                 ops.gemm(h1, L.W, pre[rs], A2=h2)
             else:
@@ -564,7 +565,8 @@ class MLPEngine:
                            None if onehot else out2[rs], head["action"], head["ent"], noise=head.get("noise"),
                            rng=head.get("rng"), eps_out=head.get("eps_out"), act_idx=head.get("act_idx"),
                            forced=head.get("forced"), flips=head.get("flips"), min_std=head.get("min_std", 0.1),
-                           max_std=head.get("max_std", 1.0), unimix=head.get("unimix", 0.01), onehot=onehot)
+                           max_std=head.get("max_std", 1.0), unimix=head.get("unimix", 0.01), onehot=onehot,
+                           act=L.act)
             return h1, out[rs], None if onehot else out2[rs]
         o = o2 = None
         if out is not None:
@@ -779,7 +781,8 @@ class RSSMEngine:
         # second output of the kernels that produce them at step t (fused when the vector GRU kernel applies).
         ops.reset_blend(v2(action_tm, A), None, first.view(TB), v2(ain, A))
         fuse = ((De % 256 == 0 and De <= 1024) or (De % 1024 == 0 and De <= 4096)) and _FUSE_BLEND
-        fuse_in = fuse and gather and _FUSE_SAMPLE_IN and ops.sample_linear_ln_ok(S, D, Hd) and Hd % 4 == 0
+        # (the sample + img_in launch is SiLU-only: another activation keeps the sample and the gather as two launches)
+        fuse_in = fuse and gather and _FUSE_SAMPLE_IN and ops.sample_linear_ln_ok(S, D, Hd, P.img_in.act) and Hd % 4 == 0
         fuse_row = _FUSE_SCAN_ROW and _FUSE_SCAN_LN and B <= 64 and ops.scan_ln_gemm_ok(Hd, SW)
         Cuts.mark("wm.fscan")  # (pipelined capture: the forward scan is a lane segment of its own)
         for t in range(T):
@@ -796,7 +799,7 @@ class RSSMEngine:
                 pass  # x1[t] came out of step t-1's fused sample + img_in launch
             elif gather:
                 ops.onehot_linear_ln(idx_in[t], D, wt_in, x1pre[t], x2=ain[t], gamma=P.img_in.g, beta=P.img_in.b,
-                                     y=x1[t], mean=m1[t], rstd=r1[t])
+                                     y=x1[t], mean=m1[t], rstd=r1[t], act=P.img_in.act)
             else:
                 dense_ln_fwd(P.img_in, sin[t], ain[t], x1pre[t], m1[t], r1[t], x1[t])
             ops.gemm(x1[t], P.gru.W, gpre[t], A2=din[t])
@@ -805,9 +808,9 @@ class RSSMEngine:
             ops.gemm(deter[t], P.obs_out.W[:, :De], x3pre[t], accumulate=True)
             if fuse_row:  # the obs_out LayerNorm rides in the stat GEMM (5 launches per step instead of 6)
                 ops.scan_ln_gemm(x3pre[t], P.obs_out.g, P.obs_out.b, x3[t], m3[t], r3[t], P.obs.W,
-                                 post_stat[t].view(B, SW), bias=P.obs.b)
+                                 post_stat[t].view(B, SW), bias=P.obs.b, act=P.obs_out.act)
             else:
-                ops.ln_act_fwd(x3pre[t], P.obs_out.g, P.obs_out.b, x3[t], m3[t], r3[t], act=True)
+                ops.ln_act_fwd(x3pre[t], P.obs_out.g, P.obs_out.b, x3[t], m3[t], r3[t], act=P.obs_out.act)
                 ops.gemm(x3[t], P.obs.W, post_stat[t].view(B, SW), bias=P.obs.b)
             if gauss:
                 ops.gauss_head_fwd(post_stat[t], post_stoch[t], post_mean[t], post_std[t],
@@ -821,7 +824,8 @@ class RSSMEngine:
                                             next_first=first[t + 1], init=s0.view(SD), init_idx=init_idx,
                                             next_out=sin[t + 1].view(B, S, D), next_idx=idx_in[t + 1].view(-1),
                                             WT=wt_in, x2=ain[t + 1], pre=x1pre[t + 1], gamma=P.img_in.g,
-                                            beta=P.img_in.b, y=x1[t + 1], mean=m1[t + 1], rstd=r1[t + 1])
+                                            beta=P.img_in.b, y=x1[t + 1], mean=m1[t + 1], rstd=r1[t + 1],
+                                            act=P.img_in.act)
             else:
                 ops.onehot_sample(post_stat[t], post_stoch[t], noise=None if q_post is None else q_post[t], rng=rng,
                                   unimix=self.unimix,
@@ -950,8 +954,10 @@ class RSSMEngine:
                 # what the two LayerNorm + SiLU backward prologues need from the forward pass, for all steps at once
                 xh3, jc3 = g("obs.xh3", (T, B, Hd)), g("obs.jc3", (T, B, Hd))
                 xh1, jc1 = g("obs.xh1", (T, B, Hd)), g("obs.jc1", (T, B, Hd))
-                ops.scan_ln_factors(v2(x3pre, Hd), P.obs_out.g, P.obs_out.b, m3.view(TB), r3.view(TB), xh3, jc3)
-                ops.scan_ln_factors(v2(x1pre, Hd), P.img_in.g, P.img_in.b, m1.view(TB), r1.view(TB), xh1, jc1)
+                ops.scan_ln_factors(v2(x3pre, Hd), P.obs_out.g, P.obs_out.b, m3.view(TB), r3.view(TB), xh3, jc3,
+                                    act=P.obs_out.act)
+                ops.scan_ln_factors(v2(x1pre, Hd), P.img_in.g, P.img_in.b, m1.view(TB), r1.view(TB), xh1, jc1,
+                                    act=P.img_in.act)
             for t in reversed(range(T)):
                 if T >= 16 and t == T // 4 - 1:
                     # (captured update: the join behind the scan is queued once the GPU is here -- a main queue blocked at
@@ -1051,7 +1057,7 @@ class RSSMEngine:
         if idx is not None:
             wt = self.ws.get("rssm.img_in_wt", (P.img_in.W.shape[1], P.img_in.W.shape[0]))
             ops.onehot_linear_ln(idx, self.D, wt, bufs["x1pre"], x2=action, gamma=P.img_in.g, beta=P.img_in.b,
-                                 y=bufs["x1"], mean=bufs["m1"], rstd=bufs["r1"])
+                                 y=bufs["x1"], mean=bufs["m1"], rstd=bufs["r1"], act=P.img_in.act)
         else:
             dense_ln_fwd(P.img_in, stoch, action, bufs["x1pre"], bufs["m1"], bufs["r1"], bufs["x1"])
         ops.gemm(bufs["x1"], P.gru.W, bufs["gpre"], A2=deter)
@@ -1063,7 +1069,7 @@ class RSSMEngine:
             ops.gemm(bufs["deter"], wcat, bufs["cat"])
         else:
             ops.gemm(bufs["deter"], P.img_out.W, bufs["x2pre"])
-        ops.ln_act_fwd(bufs["x2pre"], P.img_out.g, P.img_out.b, bufs["x2"], bufs["m2"], bufs["r2"], act=True)
+        ops.ln_act_fwd(bufs["x2pre"], P.img_out.g, P.img_out.b, bufs["x2"], bufs["m2"], bufs["r2"], act=P.img_out.act)
         if self.gauss:
             # bufs: raw [M,2S], mean / std / stoch / eps [M,S]; noise: N(0,1) draws [M,S]
             ops.gemm(bufs["x2"], P.ims.W, bufs["raw"], bias=P.ims.b)
@@ -1156,6 +1162,7 @@ class PConvLayer:
     g: Optional[torch.Tensor] = None  # channel LayerNorm scale / shift (None on the decoder's last layer)
     b: Optional[torch.Tensor] = None
     bias: Optional[torch.Tensor] = None  # only the decoder's last layer has a bias
+    act: int = 1  # activation code behind the channel LayerNorm (ops.ACT_CODES; 1 = SiLU)
 
 
 # acting path: conv layers with at most this many output pixels (all images) use im2col + GEMM
@@ -1200,7 +1207,7 @@ class ConvEncoderEngine:
             mean, rstd = ws.get(f"enc.m{i}", (R,)), ws.get(f"enc.r{i}", (R,))
             last = i == n_layers - 1
             y = ws.get(f"enc.y{i}", (N, Co * OH * OH) if last else (N, OH, OH, Co))
-            ops.ln_act_fwd(pre.view(R, Co), L.g, L.b, y if last else y.view(R, Co), mean, rstd, act=True,
+            ops.ln_act_fwd(pre.view(R, Co), L.g, L.b, y if last else y.view(R, Co), mean, rstd, act=L.act,
                            chw_group=OH * OH if last else 0)
             self._acts.append((x, pre, mean, rstd, y))
             x, H = y, OH
@@ -1219,7 +1226,7 @@ class ConvEncoderEngine:
             last = i == n_layers - 1
             dpre = ws.get(f"enc.dpre{i}", pre.shape)
             ops.ln_act_bwd(dy if last else dy.view(R, Co), pre.view(R, Co), L.g, L.b, mean, rstd, dpre.view(R, Co),
-                           _g(L.g), _g(L.b), act=True, chw_group=OH * OH if last else 0)
+                           _g(L.g), _g(L.b), act=L.act, chw_group=OH * OH if last else 0)
             ops.conv_s2_wgrad(dpre, x, _g(L.W))
             if i > 0:
                 wpt = ws.get(f"enc.wpt{i}", (4, Ci, 4 * Co))
@@ -1258,7 +1265,7 @@ class ConvDecoderEngine:
                 rows = R * OH * OH
                 mean, rstd = ws.get(f"dec.m{i}", (rows,)), ws.get(f"dec.r{i}", (rows,))
                 y = ws.get(f"dec.y{i}", (R, OH, OH, Co))
-                ops.ln_act_fwd(pre.view(rows, Co), L.g, L.b, y.view(rows, Co), mean, rstd, act=True)
+                ops.ln_act_fwd(pre.view(rows, Co), L.g, L.b, y.view(rows, Co), mean, rstd, act=L.act)
                 self._acts.append((x, pre, mean, rstd, y))
             else:
                 y = ws.get("dec.recon", (R, OH, OH, Co))
@@ -1283,7 +1290,7 @@ class ConvDecoderEngine:
             if L.g is not None:
                 dpre = ws.get(f"dec.dpre{i}", pre.shape)
                 ops.ln_act_bwd(dy.view(rows, Co), pre.view(rows, Co), L.g, L.b, mean, rstd, dpre.view(rows, Co),
-                               _g(L.g), _g(L.b), act=True)
+                               _g(L.g), _g(L.b), act=L.act)
             else:
                 dpre = dy
                 if L.bias is not None:
@@ -1326,12 +1333,14 @@ class EnsembleEngine:
     the modules' parameters and their .grad.  Activations are [K][M][U] workspace buffers keyed by the row count, so the
     replay batch (regress_fwd_bwd) and the imagined rows (disag_fwd / disag_bwd) do not share any."""
 
-    def __init__(self, name: str, bucket, layers: int, ws: Workspace, *, std: float, scale: float = 1.0, log: bool = True):
+    def __init__(self, name: str, bucket, layers: int, ws: Workspace, *, std: float, scale: float = 1.0, log: bool = True,
+                 act=True):
         if bucket.members < 2 or layers < 1:
             raise ValueError("EnsembleEngine: needs at least 2 members (the unbiased std) and 1 trunk layer")
         self.name, self.bucket, self.L, self.ws = name, bucket, int(layers), ws
         self.K = bucket.members
         self.std, self.scale, self.log = float(std), float(scale), bool(log)
+        self.act = ops.act_code(act)  # the trunk layers' activation (every member's is the same)
         self._kept = None  # (x, have_mu) of the last disag_fwd
         # scratch of ops.ens_regress_loss, zeroed ONCE: the kernel resets its own ticket
         self._loss_ws = torch.zeros(ops.ENS_LOSS_WS, dtype=F32, device=ws.device)
@@ -1359,7 +1368,7 @@ class EnsembleEngine:
         h = x
         for ((W, _), (g, _), (b, _)), (pre, mean, rstd, y) in zip(layers, acts):
             ops.ens_gemm(h, W, pre)
-            ops.ens_ln_act_fwd(pre, g, b, y, mean, rstd)
+            ops.ens_ln_act_fwd(pre, g, b, y, mean, rstd, act=self.act)
             h = y
         return h, acts
 
@@ -1373,7 +1382,8 @@ class EnsembleEngine:
             (W, gW), (g, gg), (b, gb) = layers[i]
             pre, mean, rstd, _ = acts[i]
             dpre = ws.get(f"{nm}.dpre{i}", tuple(pre.shape))
-            ops.ens_ln_act_bwd(dy, pre, g, b, mean, rstd, dpre, gg if wgrad else None, gb if wgrad else None)
+            ops.ens_ln_act_bwd(dy, pre, g, b, mean, rstd, dpre, gg if wgrad else None, gb if wgrad else None,
+                               act=self.act)
             if wgrad:
                 ops.ens_gemm(dpre, acts[i - 1][3] if i > 0 else x, gW, transA=True, transB=False, accumulate=True)
             if i > 0:

@@ -45,6 +45,29 @@ def _contig(t: torch.Tensor, name: str, dtype=F32) -> None:
         raise TypeError(f"{name}: expected a contiguous CUDA/HIP {dtype} tensor")
 
 
+# Layer activation codes of the C ABI (include/dv3hip.h, csrc/dv3_common.h), keyed by the torch.nn class name the
+# config keys act / encoder.act / decoder.act carry (the reference: getattr(torch.nn, act)(), networks.py:39).
+ACT_CODES = {"none": 0, "SiLU": 1, "ReLU": 2, "ELU": 3, "GELU": 4, "Tanh": 5, "Mish": 6}
+ACT_NAMES = {c: n for n, c in ACT_CODES.items()}
+
+
+def act_code(act) -> int:
+    """True / False / a torch.nn activation name or class / a code -> the C ABI's activation code."""
+    if act is None or isinstance(act, bool):
+        return 1 if act else 0
+    if isinstance(act, int):
+        if act not in ACT_NAMES:
+            raise NotImplementedError(f"activation code {act}: one of {sorted(ACT_NAMES)}")
+        return act
+    name = act if isinstance(act, str) else getattr(act, "__name__", type(act).__name__)
+    if name == "Identity":
+        return 0
+    if name not in ACT_CODES:
+        raise NotImplementedError(f"act {name!r} is not implemented on the HIP path: one of "
+                                  f"{[n for n in ACT_CODES if n != 'none']}")
+    return ACT_CODES[name]
+
+
 class _Profile:
     """Optional per-launch accounting (bench.py's roofline leg): HIP events around every launch on the
     launch stream, keyed by kernel, with the algorithmic FLOPs / bytes the caller declares."""
@@ -510,7 +533,7 @@ def ln_act_fwd(x, gamma, beta, y, mean=None, rstd=None, *, act=True, chw_group=0
             if t.numel() != R:
                 raise ValueError(nm + " size mismatch")
     _call("dv3_ln_act_fwd", _ptr(x), ldx, _ptr(gamma), _ptr(beta), _ptr(y), ldy, _ptr(mean), _ptr(rstd), R, N,
-          int(act), int(chw_group), _stream(),
+          act_code(act), int(chw_group), _stream(),
           key="dv3_ln_act_fwd" + (f"[{R}x{N}]" if PROFILE.by_shape else ""), nbytes=8.0 * R * N)
     return y
 
@@ -547,11 +570,11 @@ def ln_act_bwd(dy, x, gamma, beta, mean, rstd, dx, dgamma=None, dbeta=None, *, a
         # 78 -> 45 us, 1 M x 32 107 -> 93, 65 k x 128 46 -> 27)
         ws = _ln_partials(x.device)
         _call("dv3_ln_act_bwd_ws", _ptr(dy), lddy, _ptr(x), ldx, _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(rstd), _ptr(dx),
-              lddx, _ptr(dgamma), _ptr(dbeta), R, N, int(act), 0, int(accumulate_dx), _ptr(ws), ws.numel(), _stream(),
+              lddx, _ptr(dgamma), _ptr(dbeta), R, N, act_code(act), 0, int(accumulate_dx), _ptr(ws), ws.numel(), _stream(),
               key=key, nbytes=12.0 * R * N)
         return dx
     _call("dv3_ln_act_bwd", _ptr(dy), lddy, _ptr(x), ldx, _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(rstd), _ptr(dx),
-          lddx, _ptr(dgamma), _ptr(dbeta), R, N, int(act), int(chw_group), int(accumulate_dx), _stream(), key=key,
+          lddx, _ptr(dgamma), _ptr(dbeta), R, N, act_code(act), int(chw_group), int(accumulate_dx), _stream(), key=key,
           nbytes=12.0 * R * N)
     return dx
 
@@ -602,8 +625,8 @@ def scan_ln_gemm_ok(K, N) -> bool:
     return K in (256, 512, 1024) and N % 16 == 0
 
 
-def scan_ln_gemm(x, gamma, beta, y, mean, rstd, W, C, *, bias=None, accumulate=False):
-    """ln_act_fwd(act=True) and C (+)= y @ W^T + bias in ONE launch (the observe scan's obs_out LayerNorm + the
+def scan_ln_gemm(x, gamma, beta, y, mean, rstd, W, C, *, bias=None, accumulate=False, act=True):
+    """ln_act_fwd(act=act) and C (+)= y @ W^T + bias in ONE launch (the observe scan's obs_out LayerNorm + the
     posterior-logit Linear, networks.py:197-200).  y / mean / rstd may be None."""
     M, K, ldx = _rows2d(x, "x")
     N, Kw, ldw = _rows2d(W, "W")
@@ -629,8 +652,10 @@ def scan_ln_gemm(x, gamma, beta, y, mean, rstd, W, C, *, bias=None, accumulate=F
         _contig(bias, "bias")
         if bias.numel() != N:
             raise ValueError("scan_ln_gemm bias size mismatch")
-    _call("dv3_scan_ln_gemm_fwd", _ptr(x), ldx, _ptr(gamma), _ptr(beta), _ptr(y), ldy, _ptr(mean), _ptr(rstd), _ptr(W),
-          ldw, _ptr(bias), _ptr(C), ldc, M, K, N, int(bool(accumulate)), _stream(),
+    code = act_code(act)
+    _call(*(("dv3_scan_ln_gemm_fwd",) if code == 1 else ("dv3_scan_ln_gemm_fwd_ex",)), _ptr(x), ldx, _ptr(gamma),
+          _ptr(beta), _ptr(y), ldy, _ptr(mean), _ptr(rstd), _ptr(W), ldw, _ptr(bias), _ptr(C), ldc, M, K, N,
+          int(bool(accumulate)), *(() if code == 1 else (code,)), _stream(),
           key="gemm_kernel<skinny16+ln,tA=0,tB=1>", flops=2.0 * M * N * K, nbytes=4.0 * (N * K + M * (2 * K + N)))
     return C
 
@@ -639,8 +664,8 @@ def scan_lnbwd_gemm_ok(K, N) -> bool:
     return K in (256, 512, 1024) and N % 64 == 0
 
 
-def scan_ln_factors(x, gamma, beta, mean, rstd, xhat, jac):
-    """xhat = (x - mean) * rstd, jac = SiLU'(xhat * gamma + beta) for all rows of a LayerNorm + SiLU layer: what its
+def scan_ln_factors(x, gamma, beta, mean, rstd, xhat, jac, *, act=True):
+    """xhat = (x - mean) * rstd, jac = act'(xhat * gamma + beta) for all rows of a LayerNorm + act layer: what its
     backward needs from the forward pass (scan_lnbwd_gemm reads them; once per update, in front of the reverse scan)."""
     R, K, ldx = _rows2d(x, "x")
     _contig(gamma, "gamma"), _contig(beta, "beta"), _contig(mean, "mean"), _contig(rstd, "rstd")
@@ -648,8 +673,10 @@ def scan_ln_factors(x, gamma, beta, mean, rstd, xhat, jac):
     if gamma.numel() != K or beta.numel() != K or mean.numel() != R or rstd.numel() != R or xhat.numel() != R * K \
             or jac.numel() != R * K or K % 4:
         raise ValueError("scan_ln_factors sizes mismatch")
-    _call("dv3_scan_ln_factors", _ptr(x), ldx, _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(rstd), _ptr(xhat), _ptr(jac), R, K,
-          _stream(), nbytes=12.0 * R * K)
+    code = act_code(act)
+    _call(*(("dv3_scan_ln_factors",) if code == 1 else ("dv3_scan_ln_factors_ex",)), _ptr(x), ldx, _ptr(gamma), _ptr(beta),
+          _ptr(mean), _ptr(rstd), _ptr(xhat), _ptr(jac), R, K, *(() if code == 1 else (code,)), _stream(),
+          key="dv3_scan_ln_factors", nbytes=12.0 * R * K)
 
 
 def scan_lnbwd_gemm(dy, xhat, jac, gamma, rstd, dx, W, C, dgamma=None, dbeta=None):
@@ -1687,15 +1714,16 @@ def onehot_linear_ln(idx, D, WT, pre, *, x2=None, base=None, gamma=None, beta=No
                 if t.numel() != M:
                     raise ValueError(nm + " size mismatch")
     _call("dv3_onehot_linear_ln_fwd", _ptr(idx), S, int(D), _ptr(x2), ldx2, A2, _ptr(WT), ldw, _ptr(base), ldbase,
-          _ptr(pre), ldpre, _ptr(gamma), _ptr(beta), _ptr(y), ldy, _ptr(mean), _ptr(rstd), M, N, int(act), _stream(),
+          _ptr(pre), ldpre, _ptr(gamma), _ptr(beta), _ptr(y), ldy, _ptr(mean), _ptr(rstd), M, N, act_code(act), _stream(),
           key="dv3_onehot_linear_ln_fwd" + (f"[{M}x{N},S={S}]" if PROFILE.by_shape else ""),
           flops=2.0 * M * N * (S * D + A2), nbytes=4.0 * M * N * (S + 2))
     return y if y is not None else pre
 
 
-def sample_linear_ln_ok(S, D, N) -> bool:
-    """Shapes the fused posterior-sample + img_in launch takes (ops.onehot_sample_linear_ln)."""
-    return D == 32 and S <= 32 and N % 256 == 0 and N <= 1024
+def sample_linear_ln_ok(S, D, N, act=True) -> bool:
+    """Shapes (and activations: none / SiLU) the fused posterior-sample + img_in launch takes
+    (ops.onehot_sample_linear_ln); a layer with another activation runs onehot_sample + onehot_linear_ln."""
+    return D == 32 and S <= 32 and N % 256 == 0 and N <= 1024 and act_code(act) <= 1
 
 
 def onehot_sample_linear_ln(logit, out, *, next_first, init, init_idx, next_out, next_idx, WT, x2, pre, gamma, beta, y,
@@ -1711,6 +1739,9 @@ def onehot_sample_linear_ln(logit, out, *, next_first, init, init_idx, next_out,
     Mp, Np, ldpre = _rows2d(pre, "pre")
     My, Ny, ldy = _rows2d(y, "y")
     Mx, A2, ldx2 = _rows2d(x2, "x2") if x2 is not None else (M, 0, 0)
+    if act_code(act) > 1:
+        raise NotImplementedError("onehot_sample_linear_ln applies no activation or SiLU; another activation takes "
+                                  "onehot_sample followed by onehot_linear_ln(act=...)")
     if not sample_linear_ln_ok(S, D, N) or (Mp, Np) != (M, N) or (My, Ny) != (M, N) or Mx != M or Kw != S * D + A2:
         raise ValueError("onehot_sample_linear_ln shapes mismatch")
     R = M * S
@@ -1734,7 +1765,7 @@ def onehot_sample_linear_ln(logit, out, *, next_first, init, init_idx, next_out,
     _call("dv3_onehot_sample_linear_ln_fwd", _ptr(logit), _ptr(noise), _ptr(rng_state), int(rng_off), _ptr(out),
           _ptr(idx), _ptr(forced), _ptr(flips), float(unimix), int(mode), _ptr(next_first), _ptr(init), _ptr(init_idx),
           _ptr(next_out), _ptr(next_idx), S, _ptr(x2), ldx2, A2, _ptr(WT), ldw, _ptr(pre), ldpre, _ptr(gamma),
-          _ptr(beta), _ptr(y), ldy, _ptr(mean), _ptr(rstd), M, N, int(act), _stream(),
+          _ptr(beta), _ptr(y), ldy, _ptr(mean), _ptr(rstd), M, N, act_code(act), _stream(),
           key="dv3_onehot_sample_linear_ln_fwd" + (f"[{M}x{N},S={S}]" if PROFILE.by_shape else ""),
           flops=2.0 * M * N * (S * D + A2), nbytes=4.0 * M * N * (S + 2))
     return out
@@ -1742,8 +1773,8 @@ def onehot_sample_linear_ln(logit, out, *, next_first, init, init_idx, next_out,
 
 def actor_head(pre, gamma, beta, y, mean, rstd, Wm, bm, Ws, bs, out_m, out_s, action, entropy, *, noise=None,
                rng=None, eps_out=None, act_idx=None, forced=None, flips=None, min_std=0.1, max_std=1.0, unimix=0.01,
-               onehot=False):
-    """Last trunk LayerNorm+SiLU, the heads, the action sample and the entropy of the actor in one launch."""
+               onehot=False, act=True):
+    """Last trunk LayerNorm + act (SiLU by default), the heads, the action sample and the entropy of the actor in one launch."""
     M, U, ldpre = _rows2d(pre, "pre")
     My, Uy, ldy = _rows2d(y, "y")
     A = Wm.shape[0]
@@ -1777,11 +1808,12 @@ def actor_head(pre, gamma, beta, y, mean, rstd, Wm, bm, Ws, bs, out_m, out_s, ac
         if rng is None:
             raise ValueError("actor_head needs noise or an RngStream")
         rng_state, rng_off = rng.state, rng.take(M * A)
-    _call("dv3_actor_head_fwd", _ptr(pre), ldpre, _ptr(gamma), _ptr(beta), _ptr(y), ldy, _ptr(mean), _ptr(rstd), _ptr(Wm),
+    code = act_code(act)
+    _call(*(("dv3_actor_head_fwd",) if code == 1 else ("dv3_actor_head_fwd_ex",)), _ptr(pre), ldpre, _ptr(gamma), _ptr(beta), _ptr(y), ldy, _ptr(mean), _ptr(rstd), _ptr(Wm),
           _ptr(bm), _ptr(Ws), _ptr(bs), _ptr(out_m), _ptr(out_s), _ptr(noise), _ptr(rng_state), int(rng_off),
           _ptr(eps_out), _ptr(action), _ptr(entropy), _ptr(act_idx), _ptr(forced), _ptr(flips), M, U, A,
-          float(min_std), float(max_std), float(unimix), int(onehot), _stream(),
-          flops=2.0 * M * U * A * (1 if onehot else 2))
+          float(min_std), float(max_std), float(unimix), int(onehot), *(() if code == 1 else (code,)), _stream(),
+          key="dv3_actor_head_fwd", flops=2.0 * M * U * A * (1 if onehot else 2))
 
 
 def gemm_sample_ok(M, N, D, A=None) -> bool:
@@ -1794,7 +1826,8 @@ def gemm_sample(A, B, logit, onehot, *, bias=None, noise=None, rng=None, idx=Non
                 unimix=0.01, mode=False, ln=None):
     """logit [M,N] = A @ B^T + bias and, in the same launch, the one-hot sample of every group of 32 logits
     (onehot [M,N]; idx/forced int32 [M*N/32]) -- ops.gemm followed by ops.onehot_sample, fused.  ln: the
-    LayerNorm + SiLU of the layer that produced A, applied on the fly (A = its pre-activations)."""
+    LayerNorm + SiLU of the layer that produced A, applied on the fly (A = its pre-activations); SiLU only: a layer
+    with another activation runs ops.ln_act_fwd first and passes ln=None."""
     M, K, lda = _rows2d(A, "A")
     N, Kb, ldb = _rows2d(B, "B")
     Mc, Nc, ldc = _rows2d(logit, "logit")
@@ -1930,7 +1963,7 @@ def ens_gemm(A, B, C, *, bias=None, transA=False, transB=True, accumulate=False)
     return C
 
 
-def ens_ln_act_fwd(x, gamma, beta, y, mean, rstd):
+def ens_ln_act_fwd(x, gamma, beta, y, mean, rstd, *, act=True):
     """SiLU(LayerNorm(x_k) * gamma_k + beta_k) over [K][M][N]; mean / rstd [K*M] saved for the backward."""
     K, M, N, ldx, sx = _ens3d(x, "x")
     _, My, Ny, ldy, sy = _ens3d(y, "y", K)
@@ -1942,13 +1975,14 @@ def ens_ln_act_fwd(x, gamma, beta, y, mean, rstd):
     _contig(mean, "mean"), _contig(rstd, "rstd")
     if mean.numel() != K * M or rstd.numel() != K * M or N > 2048:
         raise ValueError("ens_ln_act_fwd: statistics size mismatch or N > 2048")
-    _call("dv3_ens_ln_act_fwd", _ptr(x), ldx, _ptr(gamma), _ptr(beta), sG, _ptr(y), ldy, _ptr(mean), _ptr(rstd), K, M,
-          N, _stream(), key="dv3_ens_ln_act_fwd" + (f"[{K}x{M}x{N}]" if PROFILE.by_shape else ""),
+    code = act_code(act)
+    _call(*(("dv3_ens_ln_act_fwd",) if code == 1 else ("dv3_ens_ln_act_fwd_ex",)), _ptr(x), ldx, _ptr(gamma), _ptr(beta),
+          sG, _ptr(y), ldy, _ptr(mean), _ptr(rstd), K, M, N, *(() if code == 1 else (code,)), _stream(), key="dv3_ens_ln_act_fwd" + (f"[{K}x{M}x{N}]" if PROFILE.by_shape else ""),
           nbytes=8.0 * K * M * N)
     return y
 
 
-def ens_ln_act_bwd(dy, x, gamma, beta, mean, rstd, dx, dgamma=None, dbeta=None):
+def ens_ln_act_bwd(dy, x, gamma, beta, mean, rstd, dx, dgamma=None, dbeta=None, *, act=True):
     """Backward of ens_ln_act_fwd; dgamma / dbeta [K][N] are accumulated (atomic adds).  dx must not alias dy."""
     K, M, N, ldx, sx = _ens3d(x, "x")
     strides = []
@@ -1969,8 +2003,10 @@ def ens_ln_act_bwd(dy, x, gamma, beta, mean, rstd, dx, dgamma=None, dbeta=None):
     _contig(mean, "mean"), _contig(rstd, "rstd")
     if mean.numel() != K * M or rstd.numel() != K * M or N > 2048 or K > 65535:
         raise ValueError("ens_ln_act_bwd: size mismatch")
-    _call("dv3_ens_ln_act_bwd", _ptr(dy), strides[0], _ptr(x), ldx, _ptr(gamma), _ptr(beta), sG, _ptr(mean),
-          _ptr(rstd), _ptr(dx), strides[1], _ptr(dgamma), _ptr(dbeta), K, M, N, _stream(),
+    code = act_code(act)
+    _call(*(("dv3_ens_ln_act_bwd",) if code == 1 else ("dv3_ens_ln_act_bwd_ex",)), _ptr(dy), strides[0], _ptr(x), ldx,
+          _ptr(gamma), _ptr(beta), sG, _ptr(mean), _ptr(rstd), _ptr(dx), strides[1], _ptr(dgamma), _ptr(dbeta), K, M, N,
+          *(() if code == 1 else (code,)), _stream(),
           key="dv3_ens_ln_act_bwd" + (f"[{K}x{M}x{N}]" if PROFILE.by_shape else ""), nbytes=12.0 * K * M * N)
     return dx
 

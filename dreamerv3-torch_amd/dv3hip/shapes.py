@@ -78,6 +78,23 @@ SHAPES = {
                               std_act="softplus"),
     "cfg2_gauss": dict(stoch=32, discrete=0, deter=512, hidden=512, units=512, A=6, cnn_depth=32, B=16, T=64, H=15,
                        actor_dist="normal", imag_gradient="dynamics", encoder="cnn"),
+    # layer activations other than SiLU (configs.yaml act / encoder.act / decoder.act; networks.py:39, 459, 513, 613).
+    # Optional keys act / enc_act / dec_act (default: the configs.yaml value, SiLU).  tiny_actmix gives every key
+    # another activation, so that a cross-wired key shows.
+    "tiny_elu": dict(stoch=4, discrete=4, deter=16, hidden=16, units=16, A=3, cnn_depth=2, B=3, T=6, H=4,
+                     actor_dist="normal", imag_gradient="dynamics", encoder="cnn", act="ELU", enc_act="ELU",
+                     dec_act="ELU"),
+    "tiny_actmix": dict(stoch=4, discrete=4, deter=16, hidden=16, units=16, A=5, cnn_depth=2, B=3, T=6, H=4,
+                        actor_dist="onehot", imag_gradient="reinforce", encoder="both", enc_mlp_units=24,
+                        enc_mlp_layers=2, act="GELU", enc_act="Mish", dec_act="ReLU"),
+    "tiny_gauss_tanh": dict(stoch=8, discrete=0, deter=16, hidden=16, units=16, A=3, cnn_depth=2, B=3, T=6, H=4,
+                            actor_dist="normal", imag_gradient="dynamics", encoder="cnn", act="Tanh", enc_act="Tanh",
+                            dec_act="Tanh"),
+    "tiny_p2e_elu": dict(stoch=4, discrete=4, deter=16, hidden=16, units=16, A=3, cnn_depth=2, B=3, T=6, H=4,
+                         actor_dist="normal", imag_gradient="dynamics", encoder="cnn", act="ELU", enc_act="ELU",
+                         dec_act="ELU",
+                         p2e=dict(disag_models=3, disag_layers=2, disag_units=16, disag_target="stoch", disag_offset=1,
+                                  disag_log=True, disag_action_cond=False, expl_intr_scale=1.0, expl_extr_scale=0.0)),
 }
 # walker_walk proprio keys, in the order the reference's obs_space dict would list them
 PROPRIO_KEYS: Tuple[Tuple[str, int], ...] = (("orientations", 14), ("height", 1), ("velocity", 9))
@@ -114,6 +131,12 @@ def make_config(name, device="cuda:0"):
     for key in ("mean_act", "std_act", "min_std"):
         if key in s:
             cfg["dyn_" + key] = s[key]
+    if "act" in s:
+        cfg["act"] = s["act"]
+    if "enc_act" in s:
+        cfg["encoder"]["act"] = s["enc_act"]
+    if "dec_act" in s:
+        cfg["decoder"]["act"] = s["dec_act"]
     cfg["encoder"]["cnn_depth"] = s["cnn_depth"]
     cfg["decoder"]["cnn_depth"] = s["cnn_depth"]
     if s["actor_dist"] == "onehot":

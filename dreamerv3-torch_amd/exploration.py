@@ -110,7 +110,7 @@ class Plan2Explore(nn.Module):
             # the fixed std of networks.MLP's Normal head (networks.py:614, 693-696)
             std = (head._max_std - head._min_std) / (1.0 + math.exp(-(float(head._std) + 2.0))) + head._min_std
             eng = E.EnsembleEngine("p2e", self._expl_opt.bucket, cfg.disag_layers, N_._workspace(self, dev), std=std,
-                                   scale=cfg.expl_intr_scale, log=cfg.disag_log)
+                                   scale=cfg.expl_intr_scale, log=cfg.disag_log, act=head._act_code)
             ens = (eng, models.EnsembleObjective(eng, cfg.disag_action_cond, cfg.expl_extr_scale))
             self.__dict__["_ens"] = ens
         return ens

@@ -41,7 +41,17 @@ def _workspace(mod: nn.Module, device) -> E.Workspace:
 
 def _dense_ln(seq) -> E.PDenseLN:
     lin, norm = seq[0], seq[1]
-    return E.PDenseLN(lin.weight, norm.weight, norm.bias)
+    return E.PDenseLN(lin.weight, norm.weight, norm.bias, getattr(seq, "_act_code", 1))
+
+
+def _act_module(act):
+    """The reference's `getattr(torch.nn, act)()` (networks.py:39, 459, 513, 613) for the activations the kernels
+    have -> (the torch.nn module, a parameter-free marker in the layer stack; its code for the kernels).  act: a
+    torch.nn name or class.  Anything else raises NotImplementedError naming the supported set."""
+    code = ops.act_code(act)
+    if code == 0:
+        raise NotImplementedError(f"act {act!r}: one of {[n for n in ops.ACT_CODES if n != 'none']}")
+    return getattr(nn, ops.ACT_NAMES[code])(), code
 
 
 class GRUCell(nn.Module):
@@ -79,22 +89,24 @@ class GRUCell(nn.Module):
 
 
 class DenseLNBlock(nn.Sequential):
-    """[Linear(no bias), LayerNorm(eps 1e-3), SiLU] as the reference builds its `_img_in_layers`, `_img_out_layers`
+    """[Linear(no bias), LayerNorm(eps 1e-3), act] as the reference builds its `_img_in_layers`, `_img_out_layers`
     and `_obs_out_layers` (networks.py:44-78; same child indices, so the same state_dict keys `0.weight`,
     `1.weight`, `1.bias`), callable like the nn.Sequential it is there (scm_world_model.py:138, 160, 164): one GEMM +
-    one fused LayerNorm/SiLU launch, through dv3hip.autograd.TrunkFn when gradients are wanted."""
+    one fused LayerNorm + activation launch, through dv3hip.autograd.TrunkFn when gradients are wanted."""
 
-    def __init__(self, inp, hidden):
-        super().__init__(nn.Linear(inp, hidden, bias=False), nn.LayerNorm(hidden, eps=1e-03), nn.SiLU())
+    def __init__(self, inp, hidden, act="SiLU"):
+        mod, code = _act_module(act)
+        super().__init__(nn.Linear(inp, hidden, bias=False), nn.LayerNorm(hidden, eps=1e-03), mod)
+        self._act_code = code
 
     def forward(self, x):
         W, g, b = self[0].weight, self[1].weight, self[1].bias
         if AG.wants_grad(x, W, g, b):
-            return AG.TrunkFn.apply(x, W, g, b)
+            return AG.TrunkFn.apply(x, self._act_code, W, g, b)
         x2 = x.reshape(-1, x.shape[-1]).to(torch.float32).contiguous()
         pre = torch.empty(x2.shape[0], W.shape[0], device=x.device)
         y = torch.empty_like(pre)
-        E.dense_ln_fwd(E.PDenseLN(W, g, b), x2, None, pre, None, None, y)
+        E.dense_ln_fwd(E.PDenseLN(W, g, b, self._act_code), x2, None, pre, None, None, y)
         return y.view(tuple(x.shape[:-1]) + (W.shape[0],))
 
 
@@ -106,8 +118,9 @@ class RSSM(nn.Module):
         discrete = int(discrete or 0)
         if not discrete:
             ops._gauss_acts(mean_act, std_act)  # (raises for an activation the head kernel does not have)
-        if act != "SiLU" or not norm or rec_depth != 1 or initial != "learned":
+        if not norm or rec_depth != 1 or initial != "learned":
             raise NotImplementedError("kernels implement act=SiLU, norm=True, rec_depth=1, initial=learned")
+        self._act_code = _act_module(act)[1]  # (raises for an activation the kernels do not have)
         self._stoch, self._deter, self._hidden, self._discrete = stoch, deter, hidden, discrete
         self._unimix_ratio, self._num_actions, self._embed, self._device = unimix_ratio, num_actions, embed, device
         self._min_std, self._rec_depth, self._initial = min_std, rec_depth, initial
@@ -116,7 +129,7 @@ class RSSM(nn.Module):
         stat_w = stoch * discrete if discrete else 2 * stoch  # logits, or mean_raw | std_raw (networks.py:80-91)
 
         def block(inp):
-            seq = DenseLNBlock(inp, hidden)
+            seq = DenseLNBlock(inp, hidden, act)
             seq.apply(tools.weight_init)
             return seq
 
@@ -373,7 +386,8 @@ class RSSM(nn.Module):
             # the whole scan as ONE autograd node over engine.RSSMEngine.observe_fwd / observe_bwd
             tmg = lambda x: x.to(torch.float32).transpose(0, 1).contiguous()
             dims = dict(stoch=self._stoch, discrete=self._discrete, deter=self._deter, hidden=self._hidden,
-                        num_actions=self._num_actions, embed=self._embed, unimix=self._unimix_ratio, **self._head_kw())
+                        num_actions=self._num_actions, embed=self._embed, unimix=self._unimix_ratio,
+                        act=self._act_code, **self._head_kw())
             fn = AG.ObserveFn if self._discrete else AG.ObserveGaussFn
             out = dict(zip(fn.KEYS, fn.apply(tmg(embed), tmg(action), tmg(is_first), nz.get("q_prior"),
                                              nz.get("q_post"), self._rng(), dims, *self._all_params())))
@@ -440,8 +454,9 @@ class MLP(nn.Module):
                  max_std=1.0, absmax=None, temp=0.1, unimix_ratio=0.01, outscale=1.0, symlog_inputs=False,
                  device="cuda", name="NoName"):
         super().__init__()
-        if act != "SiLU" or not norm:
+        if not norm:
             raise NotImplementedError("kernels implement act=SiLU, norm=True")
+        self._act_code = _act_module(act)[1]
         self._shape = (shape,) if isinstance(shape, int) else shape
         if self._shape is not None and not isinstance(self._shape, dict) and len(self._shape) == 0:
             self._shape = (1,)
@@ -452,7 +467,7 @@ class MLP(nn.Module):
         for i in range(layers):
             self.layers.add_module(f"{name}_linear{i}", nn.Linear(inp_dim, units, bias=False))
             self.layers.add_module(f"{name}_norm{i}", nn.LayerNorm(units, eps=1e-03))
-            self.layers.add_module(f"{name}_act{i}", nn.SiLU())
+            self.layers.add_module(f"{name}_act{i}", _act_module(act)[0])
             inp_dim = units
         self.layers.apply(tools.weight_init)
         self._n_layers = layers
@@ -472,7 +487,7 @@ class MLP(nn.Module):
     def trunk_params(self):
         nm = self._name
         return [E.PDenseLN(getattr(self.layers, f"{nm}_linear{i}").weight, getattr(self.layers, f"{nm}_norm{i}").weight,
-                           getattr(self.layers, f"{nm}_norm{i}").bias) for i in range(self._n_layers)]
+                           getattr(self.layers, f"{nm}_norm{i}").bias, self._act_code) for i in range(self._n_layers)]
 
     def params(self, key=None) -> E.PMLP:
         out = out2 = None
@@ -515,7 +530,7 @@ class MLP(nn.Module):
         flat = []
         for P in self.trunk_params():
             flat += [P.W, P.g, P.b]
-        h = AG.TrunkFn.apply(x, *flat) if flat else x
+        h = AG.TrunkFn.apply(x, self._act_code, *flat) if flat else x
         if self._shape is None:
             return h
         if isinstance(self._shape, dict):
@@ -576,15 +591,16 @@ class ImgChLayerNorm(nn.Module):
 class ConvEncoder(nn.Module):
     def __init__(self, input_shape, depth=32, act="SiLU", norm=True, kernel_size=4, minres=4):
         super().__init__()
-        if act != "SiLU" or not norm or kernel_size != 4:
+        if not norm or kernel_size != 4:
             raise NotImplementedError("kernels implement act=SiLU, norm=True, kernel_size=4")
+        self._act_code = _act_module(act)[1]
         h, w, input_ch = input_shape
         stages = int(np.log2(h) - np.log2(minres))
         in_dim, out_dim = input_ch, depth
         mods = []
         for _ in range(stages):
             mods += [Conv2dSamePad(in_channels=in_dim, out_channels=out_dim, kernel_size=4, stride=2, bias=False),
-                     ImgChLayerNorm(out_dim), nn.SiLU()]
+                     ImgChLayerNorm(out_dim), _act_module(act)[0]]
             in_dim, out_dim = out_dim, out_dim * 2
             h, w = h // 2, w // 2
         self.outdim = out_dim // 2 * h * w
@@ -594,7 +610,7 @@ class ConvEncoder(nn.Module):
 
     def conv_params(self):
         return [E.PConvLayer(self.layers[3 * i].weight, self.layers[3 * i + 1].norm.weight,
-                             self.layers[3 * i + 1].norm.bias) for i in range(self._stages)]
+                             self.layers[3 * i + 1].norm.bias, act=self._act_code) for i in range(self._stages)]
 
     @property
     def engine(self) -> E.ConvEncoderEngine:
@@ -609,7 +625,7 @@ class ConvEncoder(nn.Module):
             flat = []
             for L in self.conv_params():
                 flat += [L.W, L.g, L.b]
-            emb = AG.ConvEncoderFn.apply(x, self._size, *flat)
+            emb = AG.ConvEncoderFn.apply(x, self._size, self._act_code, *flat)
             return emb.reshape(tuple(lead) + (emb.shape[-1],))
         emb = self.engine.forward(x_f32=x, keep=False)
         return emb.reshape(tuple(lead) + (emb.shape[-1],)).clone()
@@ -619,8 +635,9 @@ class ConvDecoder(nn.Module):
     def __init__(self, feat_size, shape=(3, 64, 64), depth=32, act="SiLU", norm=True, kernel_size=4, minres=4,
                  outscale=1.0, cnn_sigmoid=False):
         super().__init__()
-        if act != "SiLU" or not norm or kernel_size != 4 or cnn_sigmoid:
+        if not norm or kernel_size != 4 or cnn_sigmoid:
             raise NotImplementedError("kernels implement act=SiLU, norm=True, kernel_size=4, cnn_sigmoid=False")
+        self._act_code = _act_module(act)[1]  # (act: a torch.nn name, or a class as the reference's default nn.ELU)
         self._shape, self._minres = shape, minres
         layer_num = int(np.log2(shape[1]) - np.log2(minres))
         out_ch = minres ** 2 * depth * 2 ** (layer_num - 1)
@@ -634,7 +651,7 @@ class ConvDecoder(nn.Module):
             out_dim = shape[0] if last else in_dim // 2
             mods.append(nn.ConvTranspose2d(in_dim, out_dim, 4, 2, padding=(1, 1), output_padding=(0, 0), bias=last))
             if not last:
-                mods += [ImgChLayerNorm(out_dim), nn.SiLU()]
+                mods += [ImgChLayerNorm(out_dim), _act_module(act)[0]]
             in_dim = out_dim
         for m in mods[:-1]:
             m.apply(tools.weight_init)
@@ -646,7 +663,7 @@ class ConvDecoder(nn.Module):
         out = []
         for i in range(self._layer_num - 1):
             out.append(E.PConvLayer(self.layers[3 * i].weight, self.layers[3 * i + 1].norm.weight,
-                                    self.layers[3 * i + 1].norm.bias))
+                                    self.layers[3 * i + 1].norm.bias, act=self._act_code))
         lastm = self.layers[3 * (self._layer_num - 1)]
         out.append(E.PConvLayer(lastm.weight, None, None, lastm.bias))
         return out
@@ -666,7 +683,7 @@ class ConvDecoder(nn.Module):
             for l in L[:-1]:
                 flat += [l.W, l.g, l.b]
             flat += [L[-1].W, L[-1].bias]
-            rec = AG.ConvDecoderFn.apply(features.reshape(-1, features.shape[-1]), self._minres, *flat)
+            rec = AG.ConvDecoderFn.apply(features.reshape(-1, features.shape[-1]), self._minres, self._act_code, *flat)
             return rec.reshape(tuple(lead) + tuple(rec.shape[1:]))
         x = features.reshape(-1, features.shape[-1]).to(torch.float32).contiguous()
         rec = self.engine.forward(x, None)

@@ -25,6 +25,28 @@ extern "C" {
 
 #define DV3_ERR_ARG 10001
 
+/* Layer activation codes (the config keys act / encoder.act / decoder.act; the reference builds
+ * getattr(torch.nn, act)() after every Linear / conv + LayerNorm, networks.py:39, 459, 513, 613).  Every `act`
+ * argument below takes one of them; any other value is rejected with DV3_ERR_ARG before a launch.  Entry points
+ * without an `act` argument apply SiLU and have an `_ex` sibling that takes the code.  dv3hip/ops.py mirrors this
+ * table as ACT_CODES.
+ *   code  name  forward                         derivative
+ *   0     none  z                               1
+ *   1     SiLU  z sigmoid(z)                    s + z s (1 - s)
+ *   2     ReLU  max(z, 0)                       z > 0 ? 1 : 0
+ *   3     ELU   z > 0 ? z : expm1(z) (alpha 1)  z > 0 ? 1 : exp(z)
+ *   4     GELU  0.5 z (1 + erf(z / sqrt 2))     Phi(z) + z phi(z)   (exact, approximate='none')
+ *   5     Tanh  tanh z                          1 - tanh^2 z
+ *   6     Mish  z tanh(softplus z)              tanh(sp) + z (1 - tanh^2(sp)) sigmoid(z)
+ * All are finite, with finite derivatives, for |z| up to 40 and beyond. */
+#define DV3_ACT_NONE 0
+#define DV3_ACT_SILU 1
+#define DV3_ACT_RELU 2
+#define DV3_ACT_ELU 3
+#define DV3_ACT_GELU 4
+#define DV3_ACT_TANH 5
+#define DV3_ACT_MISH 6
+
 int dv3_version(void);
 /* 1 when the library was built with -DDV3_DEV_SWITCHES (`build.py --dev`): only then do the DV3_* A/B environment
  * switches of the launchers (and of the Python host code, dv3hip/_dev.py) have any effect.  The shipped build
@@ -88,7 +110,7 @@ int dv3_gemm_sample_f32(int M, int N, int K, const float* A, long lda, const flo
 
 /* ---- LayerNorm(eps 1e-3) [+ SiLU] ----------------------------------------------------------------
  * y = act(LN(x) * gamma + beta), rows of length N <= 2048; mean/rstd [R] are saved for the backward
- * (may be NULL in fwd).  act: 0 none, 1 SiLU.  chw_group G > 0 addresses y (fwd) / dy (bwd) as the
+ * (may be NULL in fwd).  act: an activation code (table above; 0 none, 1 SiLU).  chw_group G > 0 addresses y (fwd) / dy (bwd) as the
  * (C,H,W) flatten of G-pixel images: element (r,c) at (r/G)*N*G + c*G + r%G (networks.py:494).
  * Replaces nn.LayerNorm + SiLU (networks.py:55-56, 66-67, 75-76, 631-633) and ImgChLayerNorm + SiLU
  * (networks.py:476-477, 552-554, 801-810).  bwd ACCUMULATES dgamma/dbeta (both or neither NULL). */
@@ -406,7 +428,8 @@ int dv3_tensorstats_multi(int count, const float* x0, long n0, const float* shif
 /* dv3_onehot_sample_fwd_ex (D = 32, with the next observe step's reset blend: next_first [M], init [S][32], init_idx [S]
  * -> next_out [M][S][32], next_idx [M][S]) followed by dv3_onehot_linear_ln_fwd on the blended indices, in ONE launch:
  * the posterior sample of obs_step t (networks.py:199-204) and the _img_in_layers of obs_step t+1 (networks.py:216-218).
- * Same draws as the stand-alone sampler (bit-equal).  N % 256 == 0, N <= 1024, S <= 32. */
+ * Same draws as the stand-alone sampler (bit-equal).  N % 256 == 0, N <= 1024, S <= 32.  act: code 0 or 1 only (any other
+ * code: DV3_ERR_ARG; such a layer takes the two launches). */
 int dv3_onehot_sample_linear_ln_fwd(const float* logit, const float* noise, const unsigned long long* rng_state,
                                     unsigned long long rng_offset, float* onehot, int* idx, const int* forced,
                                     unsigned int* flips, float unimix, int mode, const float* next_first,
@@ -425,6 +448,10 @@ int dv3_onehot_sample_linear_ln_fwd(const float* logit, const float* noise, cons
 int dv3_scan_ln_gemm_fwd(const float* x, long ldx, const float* gamma, const float* beta, float* y, long ldy,
                          float* mean, float* rstd, const float* W, long ldw, const float* bias, float* C, long ldc,
                          int M, int K, int N, int accumulate, void* stream);
+/* the same with the layer's activation code (dv3_scan_ln_gemm_fwd = code 1) */
+int dv3_scan_ln_gemm_fwd_ex(const float* x, long ldx, const float* gamma, const float* beta, float* y, long ldy,
+                            float* mean, float* rstd, const float* W, long ldw, const float* bias, float* C, long ldc,
+                            int M, int K, int N, int accumulate, int act, void* stream);
 
 /* Reverse observe scan (same file): the data-gradient few-row GEMMs dX = dY W (W [K][N] row-major; K split over
  * workgroups, partial tiles added with atomics as dv3_gemm_f32 accumulate = 2 does) with the row operation that
@@ -455,6 +482,10 @@ int dv3_scan_grubwd_gemm(const float* g, long ldg, const float* xhat, const floa
                          int De, int N, void* stream);
 int dv3_scan_ln_factors(const float* x, long ldx, const float* gamma, const float* beta, const float* mean,
                         const float* rstd, float* xhat, float* jac, long R, int K, void* stream);
+/* jac = act'(xhat gamma + beta) for the activation code `act` (dv3_scan_ln_factors = code 1); dv3_scan_lnbwd_gemm
+ * reads the factors and needs no code of its own */
+int dv3_scan_ln_factors_ex(const float* x, long ldx, const float* gamma, const float* beta, const float* mean,
+                           const float* rstd, float* xhat, float* jac, long R, int K, int act, void* stream);
 int dv3_scan_lnbwd_gemm(const float* dy, long lddy, const float* xhat, const float* jac, const float* gamma,
                         const float* rstd, float* dx, long lddx, float* dgamma, float* dbeta, const float* W, long ldb,
                         float* C, long ldc, int M, int K, int N, void* stream);
@@ -489,6 +520,13 @@ int dv3_actor_head_fwd(const float* pre, long ldpre, const float* gamma, const f
                        unsigned long long rng_offset, float* eps_out, float* action, float* entropy, int* act_idx,
                        const int* forced, unsigned int* flips, long M, int U, int A, float min_std, float max_std,
                        float unimix, int onehot, void* stream);
+/* the same with the trunk's activation code: y = act(LN(pre)) (dv3_actor_head_fwd = code 1) */
+int dv3_actor_head_fwd_ex(const float* pre, long ldpre, const float* gamma, const float* beta, float* y, long ldy,
+                          float* mean, float* rstd, const float* Wm, const float* bm, const float* Ws, const float* bs,
+                          float* out_m, float* out_s, const float* noise, const unsigned long long* rng_state,
+                          unsigned long long rng_offset, float* eps_out, float* action, float* entropy, int* act_idx,
+                          const int* forced, unsigned int* flips, long M, int U, int A, float min_std, float max_std,
+                          float unimix, int onehot, int act, void* stream);
 int dv3_transpose2d(const float* src, long lds, int R, int C, float* dst, long ldd, void* stream);
 /* Up to 12 transposes in one launch (the per-update re-packing of the weights the one-hot gathers and the reverse
  * imagination rollout read).  jobs_host: HOST array of njobs x 6 unsigned 64-bit values {src, dst, lds, ldd, R, C}
@@ -518,6 +556,12 @@ int dv3_ens_ln_act_fwd(const float* x, long ldx, const float* gamma, const float
 int dv3_ens_ln_act_bwd(const float* dy, long lddy, const float* x, long ldx, const float* gamma, const float* beta,
                        long strideG, const float* mean, const float* rstd, float* dx, long lddx, float* dgamma,
                        float* dbeta, int members, int M, int N, void* stream);
+/* the same pair with the layers' activation code (the plain entries = code 1) */
+int dv3_ens_ln_act_fwd_ex(const float* x, long ldx, const float* gamma, const float* beta, long strideG, float* y,
+                          long ldy, float* mean, float* rstd, int members, int M, int N, int act, void* stream);
+int dv3_ens_ln_act_bwd_ex(const float* dy, long lddy, const float* x, long ldx, const float* gamma, const float* beta,
+                          long strideG, const float* mean, const float* rstd, float* dx, long lddx, float* dgamma,
+                          float* dbeta, int members, int M, int N, int act, void* stream);
 /* out_k[n] (+)= sum_m x_k[m][n] (the head's bias gradient), fixed summation order. */
 int dv3_ens_colsum(const float* x, long ldx, long strideX, float* out, long strideOut, int members, int M, int N,
                    int accumulate, void* stream);
