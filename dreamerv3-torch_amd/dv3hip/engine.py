@@ -45,6 +45,12 @@ _FUSE_SCAN_LNBWD = _dev.flag("DV3_FUSE_SCAN_LNBWD", True)  # ... reverse: the tw
 _FUSE_SCAN_CS = _dev.flag("DV3_FUSE_SCAN_CS", True)  # ... reverse: carry + straight-through + logit data-gradient GEMM
 _DEFER_CONV_WGRAD = _dev.flag("DV3_DEFER_CONV_WGRAD", True)  # decoder conv weight gradients beside the reverse scan
 _FUSE_SCAN_GRUBWD = _dev.flag("DV3_FUSE_SCAN_GRUBWD", True)  # ... reverse: GRU cell backward + the data-gradient GEMM of its Linear
+# weight gradients over one-hot stoch columns as a segment sum (ops.onehot_wgrad); off: the dense TN products
+_ONEHOT_WGRAD = _dev.flag("DV3_ONEHOT_WGRAD", True)
+# ... from R * U = 2 M (rows x layer width) on: at 1024 x 512 (the world model's reward / cont heads, 0.5 M) the two launches
+# with their 128 KiB tiles take 35 us on a lane against 31 for the dense product (20 on the whole chip), at 1024 x 4096
+# (4 M) 98 against 206 (profiles/r07_onehot_ab.txt); the tiny configs stay dense with them
+_ONEHOT_WGRAD_MIN_WORK = 1 << 21
 
 
 class Lanes:
@@ -277,12 +283,19 @@ class SideStream:
             if chain:
                 Cuts.mark("wm.defer")
                 self._cut = True
+            # (optional cuts round the weight gradients behind the reverse scan: the lanes schedule replays them on the
+            # behaviour's lane behind the deferred ones, graph.UpdateRunner._pipe_iteration_lanes)
+            late = not chain and Cuts.wants("wm.post@wgrad")
+            if late:
+                Cuts.mark("wm.post@wgrad")
             with ops.gemm_group() as grp:
                 for i, f in enumerate(fns):
                     if chain and i and Cuts.wants(f"wm.defer@{i}"):
                         grp.flush()
                         Cuts.mark(f"wm.defer@{i}")  # (optional cut: the schedule may share the deferred launches between lanes)
                     f()
+            if late:
+                Cuts.mark("wm.post@enc")
             return
         if self._mode == "off" or (self._mode == "lanes" and not chain):
             self._run_all(fns)
@@ -484,6 +497,26 @@ def lin_wgrad(W, dY, x1, x2=None):
         ops.gemm(dY, x2, gW[:, k1:], transA=True, transB=False, accumulate=True)
 
 
+def lin_wgrad_onehot(ws: "Workspace", name: str, W, dY, idx, D: int, x1, x2=None):
+    """lin_wgrad(W, dY, x1, x2) where x1 [R, S*D] is the exact one-hot expansion of idx (int32 [R, S]): the stoch
+    columns of W.grad take a segment sum over the class indices (ops.onehot_wgrad) in place of the dense product with
+    the one-hot matrix; shapes the kernel does not take (ops.onehot_wgrad_ok), products too small for it to pay
+    (_ONEHOT_WGRAD_MIN_WORK) and idx None keep the dense launches.
+    name: the call site -- its partials buffer must not be shared with a launch that may be in flight on another
+    stream (the critic's and the actor's backward), so it is a Workspace buffer of its own, allocated on the warm run."""
+    R, U = dY.shape
+    S = 0 if idx is None else idx.shape[1]
+    if (idx is None or not _ONEHOT_WGRAD or R * U < _ONEHOT_WGRAD_MIN_WORK or x1.shape[1] != S * D
+            or not ops.onehot_wgrad_ok(R, U, S, D, dY.stride(0) if R > 1 else U) or dY.data_ptr() % 8):
+        lin_wgrad(W, dY, x1, x2)
+        return
+    gW = _g(W)
+    part = ws.get(f"{name}.ohwg", (ops.onehot_wgrad_partials(R, U, S, D),))
+    ops.onehot_wgrad(dY, idx, D, gW[:, :S * D] if x2 is not None else gW, part)
+    if x2 is not None:
+        ops.gemm(dY, x2, gW[:, S * D:], transA=True, transB=False, accumulate=True)
+
+
 # ---------------------------------------------------------------------------------------------
 # MLP trunk + head Linears (networks.MLP, networks.py:588-681) on a row block, fwd / bwd
 # ---------------------------------------------------------------------------------------------
@@ -578,11 +611,13 @@ class MLPEngine:
         return h1, o, o2
 
     def backward(self, x1, x2, rows: slice, dout=None, dout2=None, *, wgrad: bool, dx1=None, dx2=None,
-                 acc_dx=False, dh=None, defer=None):
+                 acc_dx=False, dh=None, defer=None, idx=None, D=0):
         """Back-propagate rows `rows` of the stored activations.  x1/x2: the inputs those rows were computed
         from (same row count).  dout/dout2: gradients of the head Linears' outputs for those rows; dh: gradient
         on the trunk output itself (head-less MLPs such as the proprio encoder).  defer: a list that receives
-        the weight-gradient launches as callables instead of running them inline (see SideStream)."""
+        the weight-gradient launches as callables instead of running them inline (see SideStream).
+        idx (int32 [R,S]) + D: x1 is the exact one-hot expansion of idx, as in forward(): the first layer's weight
+        gradient over the stoch columns is then a segment sum (lin_wgrad_onehot)."""
         P, ws, nm = self.P, self.ws, self.name
         acts, _, _ = self._bufs(self.total)
         R = x1.shape[0]
@@ -614,8 +649,11 @@ class MLPEngine:
             dpre = ws.get(f"{nm}.dpre{i}", (R, pre.shape[1]))
             dense_ln_bwd_pre(L, dy, pre[rows], mean[rows], rstd[rows], dpre, wgrad=wgrad)
             if wgrad:
-                def _wg(L=L, dpre=dpre, xin1=xin1, xin2=xin2):
-                    lin_wgrad(L.W, dpre, xin1, xin2)
+                def _wg(L=L, dpre=dpre, xin1=xin1, xin2=xin2, i=i):
+                    if i == 0 and idx is not None:
+                        lin_wgrad_onehot(ws, nm, L.W, dpre, idx, D, xin1, xin2)
+                    else:
+                        lin_wgrad(L.W, dpre, xin1, xin2)
                 (defer.append if defer is not None else (lambda f: f()))(_wg)
             if i > 0:
                 dprev = ws.get(f"{nm}.dy{i - 1}", (R, xin1.shape[1]))
@@ -1277,7 +1315,9 @@ class ConvDecoderEngine:
             x, H = y, OH
         return x
 
-    def backward(self, drecon, dx1, dx2, *, acc_dx=False, defer=None):
+    def backward(self, drecon, dx1, dx2, *, acc_dx=False, defer=None, idx=None, D=0):
+        """idx (int32 [R,S]) + D: the x1 of forward() is the exact one-hot expansion of idx -- the Linear's weight
+        gradient over those columns is then a segment sum (lin_wgrad_onehot)."""
         ws = self.ws
         run = defer.append if defer is not None else (lambda f: f())
         dy = drecon
@@ -1312,7 +1352,7 @@ class ConvDecoderEngine:
         x1, x2 = self._x
 
         def _lin_wg():
-            lin_wgrad(self.lin.W, dh0, x1, x2)
+            lin_wgrad_onehot(ws, "dec.lin", self.lin.W, dh0, idx, D, x1, x2)
             ops.colsum(dh0, _g(self.lin.b), accumulate=True)
 
         run(_lin_wg)

@@ -220,7 +220,8 @@ class SegmentRecorder:
 _PIPE_PLAN = dict(on=_dev.flag("DV3_PIPE", True), a_split=_dev.value("DV3_PIPE_A_SPLIT", 0) or None,
                   c_split=_dev.value("DV3_PIPE_C_SPLIT", 0) or None, defer=_dev.value("DV3_PIPE_DEFER", "auto", str),
                   late=_dev.flag("DV3_PIPE_LATE", True), mode=_dev.value("DV3_PIPE_MODE", "auto", str),
-                  defer_split=_dev.value("DV3_PIPE_DEFER_SPLIT", 0) or None)
+                  defer_split=_dev.value("DV3_PIPE_DEFER_SPLIT", 0) or None,
+                  late_wgrads=_dev.flag("DV3_PIPE_LATE_WGRADS", True))
 
 
 class PhaseRecorder:
@@ -690,7 +691,8 @@ class UpdateRunner:
             lane_wm = lambda lb: {"wm.fscan": "scan", "wm.fscan2": "scan", "wm.rscan": "scan", "wm.rscan2": "scan"}.get(lb, "main")
         if mode == "lanes":
             # each phase on a lane of its own from end to end: its segments are captured on that lane's stream
-            lane_wm = lambda lb: "side" if lb == "wm.defer" else "scan"  # ("wm.defer@i", the rest of them: on the scan lane)
+            # ("wm.defer@i", the rest of them: on the scan lane; "wm.post@wgrad", the scan's weight gradients: on the side lane)
+            lane_wm = lambda lb: "side" if lb in ("wm.defer", "wm.post@wgrad") else "scan"
             lane_beh = lambda lb: "side"
         opt_cuts = [f"bh.A@{plan['a_split']}"] if plan.get("a_split") else []
         opt_cuts += [f"bh.C@{plan['c_split']}"] if plan.get("c_split") else []
@@ -702,6 +704,11 @@ class UpdateRunner:
         # cfg 2 end within 0.03 ms of each other with ALL of them on the behaviour's lane: 13.21 ms against 13.35 / 13.43 with
         # the last three / six on the other lane)
         w_cuts = [f"wm.defer@{plan['defer_split']}"] if (plan.get("defer_split") and mode == "lanes") else []
+        # (late_wgrads: the reverse scan's batched weight gradients -- every operand is final when the scan ends and nothing
+        # reads them before Adam -- leave the world model's lane for the behaviour's, which the segment-sum weight gradients
+        # (ops.onehot_wgrad) left ~0.8 ms short of the other: profiles/r07_pipe_lanes.txt)
+        if plan.get("late_wgrads", True) and mode == "lanes":
+            w_cuts += ["wm.post@wgrad", "wm.post@enc"]
         with tools.rng_override(key_dev, rng_wm):
             W = PhaseRecorder(pool_w, dev, lanes, lane_wm, "wm.pre", optional=w_cuts).record(
                 lambda: wm.train_fwd_bwd(self._static), at_end=rng_wm.finish_phase)
@@ -722,7 +729,7 @@ class UpdateRunner:
         self._pipe = dict(W=W.segments, B=B.segments, wopt=gw, bopt=gb, cap=cap, rng_wm=rng_wm, rng_beh=rng_beh,
                           lanes=lanes, entered=False, shared=tools.default_rng(key_dev), mode=mode,
                           ev={k: mk() for k in ("tail", "fork1", "q1", "mid", "fork2", "q2")},
-                          ev2={k: (mk() if k == "mid" else torch.cuda.Event()) for k in ("load", "start", "mid", "defer", "wopt")},
+                          ev2={k: (mk() if k == "mid" else torch.cuda.Event()) for k in ("load", "start", "mid", "scan", "defer", "wopt")},
                           ring=[mk(), mk()])
 
     def _pipe_enter(self):
@@ -753,12 +760,14 @@ class UpdateRunner:
         launches takes only 1.5-1.8x as long on 128 compute units as on 256 (every launch pays ~4-5 us that do not scale
         with its work), so two half-chip streams of independent work deliver ~1.25x the whole chip's serial rate.
 
-          X (scan lane)  [load . wm.pre] -e_start-> [fwd scan . wm.mid] [rev scan . wm.post] -e_defer-> [all-reduce . Adam] -e_wopt->
-          Y (side lane)  -e_wopt(k)-> [bh.start] [rollout . heads . reverse rollout . actor] [all-reduce x2 . Adam x2] -e_mid-> [wm.defer]
+          X (scan lane)  [load . wm.pre] -e_start-> [fwd scan . wm.mid] [rev scan . wm.post] -e_scan-> [encoder backward] -e_defer-> [all-reduce . Adam] -e_wopt->
+          Y (side lane)  -e_wopt(k)-> [bh.start] [rollout . heads . reverse rollout . actor] [all-reduce x2 . Adam x2] -e_mid-> [wm.defer] -e_scan-> [scan wgrads]
 
         Cross-lane events: the posterior of update k is copied out (bh.start) before scan k+1 overwrites it; the
-        deferred weight gradients of update k+1 follow its decoder / heads (e_mid); world-model Adam k+1 follows the last
-        read of the weights by behaviour k and the deferred gradients (e_defer); behaviour k+1 follows Adam k+1 (e_wopt)."""
+        deferred weight gradients of update k+1 follow its decoder / heads (e_mid), the reverse scan's batched weight
+        gradients its reverse scan (e_scan; "wm.post@wgrad", plan switch late_wgrads); world-model Adam k+1 follows the last
+        read of the weights by behaviour k and both groups of deferred gradients (e_defer); behaviour k+1 follows Adam k+1
+        (e_wopt)."""
         P = self._pipe
         W, B, ev = dict(P["W"]), dict(P["B"]), P["ev2"]
         L = P["lanes"].streams
@@ -797,7 +806,9 @@ class UpdateRunner:
         X.wait_event(ev["start"])
         run(W, ["wm.fscan", "wm.fscan2", "wm.mid"], X)
         ev["mid"].record(X)
-        run(W, ["wm.rscan", "wm.rscan2", "wm.post"] + [lb for lb in W if lb.startswith("wm.defer@")], X)
+        run(W, ["wm.rscan", "wm.rscan2", "wm.post"], X)
+        ev["scan"].record(X)  # (the reverse scan and the encoder-output gradient are over: "wm.post@wgrad" may start)
+        run(W, ["wm.post@enc"] + [lb for lb in W if lb.startswith("wm.defer@")], X)
         with torch.cuda.stream(Y):
             self.beh._actor_opt.bucket.allreduce()
             self.beh._value_opt.bucket.allreduce()
@@ -805,6 +816,9 @@ class UpdateRunner:
             self._sink(1, P["cap"]["beh_out"][-1])
         Y.wait_event(ev["mid"])
         run(W, ["wm.defer"], Y)
+        if "wm.post@wgrad" in W:
+            Y.wait_event(ev["scan"])
+            run(W, ["wm.post@wgrad"], Y)
         ev["defer"].record(Y)
         X.wait_event(ev["defer"])
         with torch.cuda.stream(X):

@@ -1720,6 +1720,57 @@ def onehot_linear_ln(idx, D, WT, pre, *, x2=None, base=None, gamma=None, beta=No
     return y if y is not None else pre
 
 
+def onehot_wgrad_ok(R, U, S, D, ldy=None, ldw=None) -> bool:
+    """Shapes dv3_onehot_wgrad takes (csrc/onehot_wgrad.hip): an even number of dY columns with an even row pitch
+    (8-byte loads), groups in fours (a 4-lane quad shares a group), the [S*D][32] accumulator tile within 128 KiB of
+    LDS.  Everything else keeps the dense TN product (engine.lin_wgrad)."""
+    return (R >= 1 and U >= 2 and U % 2 == 0 and S >= 4 and S % 4 == 0 and S <= 64 and D >= 1 and S * D <= 1024
+            and (ldy is None or (ldy % 2 == 0 and ldy >= U)) and (ldw is None or ldw >= S * D))
+
+
+def onehot_wgrad_splits(R, U, cus=256) -> int:
+    """Row splits of one launch: a workgroup per compute unit of the queue (the 128 KiB tile allows no second one)
+    over the ceil(U/32) column blocks, and at least 256 rows per split (a split costs its whole tile in partials)."""
+    return max(1, min(cus // -(-U // 32), R // 256))
+
+
+def onehot_wgrad_partials(R, U, S, D) -> int:
+    """Floats of partials for a launch on any queue (the whole chip's split count: the buffer of a call site is
+    allocated once, on the warm run, whichever lane the captured launch lands on)."""
+    return onehot_wgrad_splits(R, U) * -(-U // 32) * S * D * 32
+
+
+def onehot_wgrad(dY, idx, D, gW, partials, *, nsplit=None):
+    """gW[:, :S*D] += dY^T @ onehot(idx, D): the weight gradient of a Linear over the exact one-hot columns of its
+    input as a segment sum.  dY [R,U] and gW [U, >=S*D] may be row-strided views; idx int32 [R,S] contiguous.
+    partials: float32 scratch of at least onehot_wgrad_partials(R, U, S, D) elements that no other launch in flight
+    uses (a Workspace buffer per call site).  Bit-reproducible: no atomics, fixed split order."""
+    _contig(idx, "idx", torch.int32)
+    if idx.dim() != 2:
+        raise ValueError("idx must be [R,S]")
+    R, S = idx.shape
+    Ry, U, ldy = _rows2d(dY, "dY")
+    Ug, Kg, ldw = _rows2d(gW, "gW")
+    SD = S * int(D)
+    if Ry != R or Ug != U or Kg < SD:
+        raise ValueError(f"onehot_wgrad: dY {tuple(dY.shape)} idx {tuple(idx.shape)} D {D} gW {tuple(gW.shape)}")
+    if not onehot_wgrad_ok(R, U, S, int(D), ldy, ldw) or dY.data_ptr() % 8:
+        raise ValueError(f"onehot_wgrad: unsupported shape R {R} U {U} S {S} D {D} ldy {ldy} (ops.onehot_wgrad_ok)")
+    _contig(partials, "partials")
+    s = _stream()
+    if nsplit is None:
+        nsplit = onehot_wgrad_splits(R, U, LANE_STREAMS.get(s, 256))
+    nsplit = int(nsplit)
+    if not 1 <= nsplit <= R or partials.numel() < nsplit * -(-U // 32) * SD * 32:
+        raise ValueError(f"onehot_wgrad: {nsplit} splits of {R} rows need {nsplit * -(-U // 32) * SD * 32} floats of "
+                         f"partials, got {partials.numel()}")
+    # priced as the dense product it replaces (as the gather layers are): update_gflop stays comparable across commits
+    _call("dv3_onehot_wgrad", _ptr(dY), ldy, _ptr(idx), R, U, S, int(D), _ptr(gW), ldw, _ptr(partials),
+          partials.numel(), nsplit, s, key="dv3_onehot_wgrad" + (f"[{U}x{SD}x{R}]" if PROFILE.by_shape else ""),
+          flops=2.0 * R * U * SD, nbytes=4.0 * (R * U + R * S + 2 * U * SD))
+    return gW
+
+
 def sample_linear_ln_ok(S, D, N, act=True) -> bool:
     """Shapes (and activations: none / SiLU) the fused posterior-sample + img_in launch takes
     (ops.onehot_sample_linear_ln); a layer with another activation runs onehot_sample + onehot_linear_ln."""

@@ -292,7 +292,8 @@ class WorldModel(nn.Module):
             drecon = ws.get("wm.drecon", recon.shape)
             ops.mse_image(recon, st["image"], limg, drecon, upstream=up, perm=(B, T))
             ops.dot_accumulate(limg, acc[1:2], scale=up)
-            dec_eng.backward(drecon, gs.view(TB, SD), gd.view(TB, De), acc_dx=False, defer=deferred)
+            dec_eng.backward(drecon, gs.view(TB, SD), gd.view(TB, De), acc_dx=False, defer=deferred,
+                             idx=out["post_idx"].view(TB, S) if E._GATHER_OBS and not gauss else None, D=D)
             # (pipelined update, lanes mode: the deferred launches behind this index -- the heads' weight gradients -- may
             # run on the world model's own lane, graph.UpdateRunner._capture_pipe)
             self._defer_heads_from = len(deferred)
@@ -337,7 +338,7 @@ class WorldModel(nn.Module):
         ops.disc_logprob_bwd(r_logits, reward_tm.view(TB), up_r, dr)
         g_r = "reward" in grad_heads
         reng.backward(ps, dt, slice(0, TB), dout=dr, wgrad=True, dx1=gs.view(TB, SD) if g_r else None,
-                      dx2=gd.view(TB, De) if g_r else None, acc_dx=True, defer=deferred)
+                      dx2=gd.view(TB, De) if g_r else None, acc_dx=True, defer=deferred, idx=pidx, D=D)
         # continue head
         ceng = self.heads["cont"].engine_for(".wm")
         if pidx is not None:
@@ -351,7 +352,7 @@ class WorldModel(nn.Module):
         ops.bernoulli_logprob_bwd(c_logit.view(TB), cont_tm.view(TB), up_c, dc.view(TB))
         g_c = "cont" in grad_heads
         ceng.backward(ps, dt, slice(0, TB), dout=dc, wgrad=True, dx1=gs.view(TB, SD) if g_c else None,
-                      dx2=gd.view(TB, De) if g_c else None, acc_dx=True, defer=deferred)
+                      dx2=gd.view(TB, De) if g_c else None, acc_dx=True, defer=deferred, idx=pidx, D=D)
         # KL
         if gauss:
             # gradients on the four statistics; the scan's backward folds them through the heads' activations
@@ -907,7 +908,8 @@ class ImagBehavior(nn.Module):
                 ops.disc_logprob_fwd(v_logits[:R], slow.view(R), lp2)
                 ops.dot_accumulate(lp2, acc[1:2], w=up_v)
                 ops.disc_logprob_bwd(v_logits[:R], slow.view(R), up_v, dvl, accumulate=True)
-            veng.backward(fs[:R], fd[:R], slice(0, R), dout=dvl, wgrad=True)
+            veng.backward(fs[:R], fd[:R], slice(0, R), dout=dvl, wgrad=True, idx=None if fidx is None else fidx[:R],
+                          D=D)
 
         E.Cuts.mark("bh.B@critic")
         side = E.SideStream(fs.device)
@@ -992,7 +994,8 @@ class ImagBehavior(nn.Module):
                                     dlogp.view(HN)[:R] if use_logp else None, dmean,
                                     unimix=cfg.actor["unimix_ratio"], accumulate=not reinforce)
             dstd = None
-        im["actor"].backward(fs[:R], fd[:R], slice(0, R), dout=dmean, dout2=dstd, wgrad=True)
+        im["actor"].backward(fs[:R], fd[:R], slice(0, R), dout=dmean, dout2=dstd, wgrad=True,
+                             idx=None if fidx is None else fidx[:R], D=D)
         side.join()
         # ---- metrics + optimizers
         ops.dot_accumulate(ent.view(HN), acc[2:3], scale=1.0 / HN)

@@ -533,6 +533,15 @@ int dv3_transpose2d(const float* src, long lds, int R, int C, float* dst, long l
  * (device pointers as integers), consumed before the call returns. */
 int dv3_transpose2d_many(int njobs, const unsigned long long* jobs_host, void* stream);
 int dv3_onehot_to_idx(const float* onehot, int* idx, long R, int D, void* stream);
+/* Weight gradient of such a Linear over its one-hot columns (csrc/onehot_wgrad.hip):
+ * gW[u*ldw + s*D + d] += sum over the rows m with idx[m][s] == d of dY[m*ldy + u]  (= dY^T @ onehot(idx), a segment sum
+ * of R*S*U additions).  Two launches: per (32 columns of dY, row split) an accumulator tile in LDS, written whole to
+ * `partials`, then gW += the partials in ascending split order -- no atomics, the same bits on every call.
+ * idx int32 [R,S] row-contiguous, classes outside [0, D) are clamped; U, ldy even, dY 8-byte aligned, S % 4 == 0,
+ * S <= 64, S*D <= 1024, ldw >= S*D.  partials: nsplit * ceil(U/32) * S*D * 32 floats (partials_floats = its capacity),
+ * 16-byte aligned, private to the call until it has run; 1 <= nsplit <= R row splits of ceil(R/nsplit) rows. */
+int dv3_onehot_wgrad(const float* dY, long ldy, const int* idx, long R, int U, int S, int D, float* gW, long ldw,
+                     float* partials, long partials_floats, int nsplit, void* stream);
 
 /* ---- member-batched ensemble kernels (csrc/ensops.hip) -----------------------------------------------------------
  * Plan2Explore's ensemble (reference exploration.py:40-135): K = disag_models MLPs on one shared input.  Activations
