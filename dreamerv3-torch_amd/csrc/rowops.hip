@@ -1221,6 +1221,255 @@ extern "C" int dv3_gru_bwd(const float* dh_new, long lddhn, const float* p, long
   return (int)hipGetLastError();
 }
 
+// ================================================================================================
+// Layers without a LayerNorm (norm / encoder.norm / decoder.norm: False).  The reference then drops the nn.LayerNorm /
+// ImgChLayerNorm module and nothing else (networks.py:53-78, 472, 529-548, 627-633, 751-754): a layer is act(W x), the
+// GRU splits its raw pre-activations.  Element-wise and bandwidth-bound: no row statistics, no parameter gradients,
+// one 16-byte chunk (or one float) per thread and trip of a grid-stride loop.
+// ================================================================================================
+constexpr int kActGridCap = 2048;  // workgroups of 256: 8 per compute unit on 256 of them; more rows take further trips
+
+// flat element e of an [R][n] index space -> (row, column); 32-bit division whenever e allows it
+__device__ __forceinline__ void flat_rc(long e, int n, long& r, int& c) {
+  if (e < (1L << 31)) {
+    const unsigned q = (unsigned)e / (unsigned)n;
+    r = (long)q;
+    c = (int)((unsigned)e - q * (unsigned)n);
+  } else {
+    r = e / n;
+    c = (int)(e - r * n);
+  }
+}
+
+// y = act(x).  VEC: N % 4 == 0, plain row-major, 16-byte aligned rows.  G as in act_addr (y only).
+template <bool VEC>
+__global__ __launch_bounds__(256) void act_fwd_kernel(const float* __restrict__ x, long ldx, float* __restrict__ y,
+                                                      long ldy, long R, int N, int act, int G) {
+  const int n = VEC ? N / 4 : N;
+  const long total = R * n;
+  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+    long r;
+    int c;
+    flat_rc(e, n, r, c);
+    if constexpr (VEC) {
+      const f4 v = *reinterpret_cast<const f4*>(x + r * ldx + 4 * c);
+      f4 o;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) o[k] = actf_(v[k], act);
+      *reinterpret_cast<f4*>(y + r * ldy + 4 * c) = o;
+    } else {
+      y[act_addr(r, c, ldy, N, G)] = actf_(x[r * ldx + c], act);
+    }
+  }
+}
+
+// dx (+)= dy * act'(x).  G addresses dy.  dx may be dy (in place): every thread reads its element before it writes.
+template <bool VEC>
+__global__ __launch_bounds__(256) void act_bwd_kernel(const float* dy, long lddy, const float* __restrict__ x, long ldx,
+                                                      float* dx, long lddx, long R, int N, int act, int G,
+                                                      int accumulate_dx) {
+  const int n = VEC ? N / 4 : N;
+  const long total = R * n;
+  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+    long r;
+    int c;
+    flat_rc(e, n, r, c);
+    if constexpr (VEC) {
+      const f4 v = *reinterpret_cast<const f4*>(x + r * ldx + 4 * c);
+      const f4 g = *reinterpret_cast<const f4*>(dy + r * lddy + 4 * c);
+      f4* o = reinterpret_cast<f4*>(dx + r * lddx + 4 * c);
+      f4 d;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) d[k] = g[k] * dactf_(v[k], act);
+      *o = accumulate_dx ? (*o + d) : d;
+    } else {
+      const float d = dy[act_addr(r, c, lddy, N, G)] * dactf_(x[r * ldx + c], act);
+      float* o = dx + r * lddx + c;
+      *o = accumulate_dx ? (*o + d) : d;
+    }
+  }
+}
+
+// GRU gates on the raw pre-activations p [M][3 De] = r | c | u (GRUCell.forward without its LayerNorm,
+// networks.py:760-768): r = sigmoid(p_r), c = tanh(r p_c), u = sigmoid(p_u - 1), h' = u c + (1 - u) h.
+// One hidden unit (VEC: four) per thread.
+template <bool VEC>
+__global__ __launch_bounds__(256) void gru_nonorm_fwd_kernel(const float* __restrict__ p, long ldp,
+                                                             const float* __restrict__ h, long ldh,
+                                                             float* __restrict__ hn, long ldhn, int M, int De,
+                                                             NextBlend nb) {
+  constexpr int W = VEC ? 4 : 1;
+  const int n = De / W;
+  const long total = (long)M * n;
+  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+    long r;
+    int c;
+    flat_rc(e, n, r, c);
+    const int j = W * c;
+    const float* pr = p + r * ldp + j;
+    alignas(16) float vr[W], vc[W], vu[W], hp[W], o[W];
+    if constexpr (VEC) {
+      *reinterpret_cast<f4*>(vr) = *reinterpret_cast<const f4*>(pr);
+      *reinterpret_cast<f4*>(vc) = *reinterpret_cast<const f4*>(pr + De);
+      *reinterpret_cast<f4*>(vu) = *reinterpret_cast<const f4*>(pr + 2 * De);
+      *reinterpret_cast<f4*>(hp) = *reinterpret_cast<const f4*>(h + r * ldh + j);
+    } else {
+      vr[0] = pr[0], vc[0] = pr[De], vu[0] = pr[2 * De], hp[0] = h[r * ldh + j];
+    }
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+      const float rg = sigmoidf_(vr[k]);
+      const float cg = tanhf(rg * vc[k]);
+      const float ug = sigmoidf_(vu[k] - 1.f);
+      o[k] = ug * cg + (1.f - ug) * hp[k];
+    }
+    if constexpr (VEC) *reinterpret_cast<f4*>(hn + r * ldhn + j) = *reinterpret_cast<const f4*>(o);
+    else hn[r * ldhn + j] = o[0];
+    if (nb.out) {  // the next observe step's reset blend of this state (networks.py:183-191), fused here
+      const float m = nb.first[r];
+#pragma unroll
+      for (int k = 0; k < W; ++k) nb.out[r * nb.ld + j + k] = o[k] * (1.f - m) + nb.init[j + k] * m;
+    }
+  }
+}
+
+// Backward of the gates above, g = dh':  dp_u = g (c - h) u (1 - u);  t = g u (1 - c^2), dp_c = t r,
+// dp_r = t p_c r (1 - r);  dh (+)= g (1 - u).  dh may be dh' and dp may be p (in place): every thread reads all
+// of its inputs before its first store.
+template <bool VEC>
+__global__ __launch_bounds__(256) void gru_nonorm_bwd_kernel(const float* dhn, long lddhn, const float* p, long ldp,
+                                                             const float* h, long ldh, float* dp, long lddp,
+                                                             float* dh, long lddh, int M, int De, int accumulate_dh) {
+  constexpr int W = VEC ? 4 : 1;
+  const int n = De / W;
+  const long total = (long)M * n;
+  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+    long r;
+    int c;
+    flat_rc(e, n, r, c);
+    const int j = W * c;
+    const float* pr = p + r * ldp + j;
+    float* dpr = dp + r * lddp + j;
+    float* dhr = dh + r * lddh + j;
+    alignas(16) float vr[W], vc[W], vu[W], hp[W], g[W], old[W], dr[W], dc[W], du[W], dhd[W];
+    if constexpr (VEC) {
+      *reinterpret_cast<f4*>(vr) = *reinterpret_cast<const f4*>(pr);
+      *reinterpret_cast<f4*>(vc) = *reinterpret_cast<const f4*>(pr + De);
+      *reinterpret_cast<f4*>(vu) = *reinterpret_cast<const f4*>(pr + 2 * De);
+      *reinterpret_cast<f4*>(hp) = *reinterpret_cast<const f4*>(h + r * ldh + j);
+      *reinterpret_cast<f4*>(g) = *reinterpret_cast<const f4*>(dhn + r * lddhn + j);
+      if (accumulate_dh) *reinterpret_cast<f4*>(old) = *reinterpret_cast<const f4*>(dhr);
+    } else {
+      vr[0] = pr[0], vc[0] = pr[De], vu[0] = pr[2 * De], hp[0] = h[r * ldh + j], g[0] = dhn[r * lddhn + j];
+      if (accumulate_dh) old[0] = dhr[0];
+    }
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+      const float rg = sigmoidf_(vr[k]);
+      const float cg = tanhf(rg * vc[k]);
+      const float ug = sigmoidf_(vu[k] - 1.f);
+      const float t = g[k] * ug * (1.f - cg * cg);
+      du[k] = g[k] * (cg - hp[k]) * ug * (1.f - ug);
+      dc[k] = t * rg;
+      dr[k] = t * vc[k] * rg * (1.f - rg);
+      dhd[k] = g[k] * (1.f - ug);
+      if (accumulate_dh) dhd[k] += old[k];
+    }
+    if constexpr (VEC) {
+      *reinterpret_cast<f4*>(dpr) = *reinterpret_cast<const f4*>(dr);
+      *reinterpret_cast<f4*>(dpr + De) = *reinterpret_cast<const f4*>(dc);
+      *reinterpret_cast<f4*>(dpr + 2 * De) = *reinterpret_cast<const f4*>(du);
+      *reinterpret_cast<f4*>(dhr) = *reinterpret_cast<const f4*>(dhd);
+    } else {
+      dpr[0] = dr[0], dpr[De] = dc[0], dpr[2 * De] = du[0], dhr[0] = dhd[0];
+    }
+  }
+}
+
+static bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr,
+                      const void* e = nullptr) {
+  return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d | (uintptr_t)e) & 15) == 0;
+}
+static unsigned act_grid(long work) {
+  const long blocks = (work + 255) / 256;
+  return (unsigned)(blocks < kActGridCap ? blocks : kActGridCap);
+}
+
+extern "C" int dv3_act_fwd(const float* x, long ldx, float* y, long ldy, long R, int N, int act, int chw_group,
+                           void* stream) {
+  if (R <= 0) return 0;
+  if (N <= 0 || !x || !y || ldx < N || (chw_group <= 0 && ldy < N) || !dv3_act_ok(act)) return DV3_ERR_ARG;
+  if (chw_group > 0 && R % chw_group != 0) return DV3_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  if (chw_group <= 0 && N % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && aligned16(x, y))
+    hipLaunchKernelGGL((act_fwd_kernel<true>), dim3(act_grid(R * (N / 4))), dim3(256), 0, s, x, ldx, y, ldy, R, N, act, 0);
+  else
+    hipLaunchKernelGGL((act_fwd_kernel<false>), dim3(act_grid(R * N)), dim3(256), 0, s, x, ldx, y, ldy, R, N, act,
+                       chw_group);
+  return (int)hipGetLastError();
+}
+
+extern "C" int dv3_act_bwd(const float* dy, long lddy, const float* x, long ldx, float* dx, long lddx, long R, int N,
+                           int act, int chw_group, int accumulate_dx, void* stream) {
+  if (R <= 0) return 0;
+  if (N <= 0 || !dy || !x || !dx || ldx < N || lddx < N || (chw_group <= 0 && lddy < N) || !dv3_act_ok(act))
+    return DV3_ERR_ARG;
+  if (chw_group > 0 && R % chw_group != 0) return DV3_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  if (chw_group <= 0 && N % 4 == 0 && ldx % 4 == 0 && lddy % 4 == 0 && lddx % 4 == 0 && aligned16(dy, x, dx))
+    hipLaunchKernelGGL((act_bwd_kernel<true>), dim3(act_grid(R * (N / 4))), dim3(256), 0, s, dy, lddy, x, ldx, dx, lddx, R,
+                       N, act, 0, accumulate_dx);
+  else
+    hipLaunchKernelGGL((act_bwd_kernel<false>), dim3(act_grid(R * N)), dim3(256), 0, s, dy, lddy, x, ldx, dx, lddx, R, N,
+                       act, chw_group, accumulate_dx);
+  return (int)hipGetLastError();
+}
+
+static int gru_nonorm_fwd_impl(const float* p, long ldp, const float* h, long ldh, float* h_new, long ldhn, int M, int De,
+                               NextBlend nb, void* stream) {
+  if (M <= 0) return 0;
+  if (De <= 0 || !p || !h || !h_new || ldp < 3L * De || ldh < De || ldhn < De) return DV3_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  if (De % 4 == 0 && ldp % 4 == 0 && ldh % 4 == 0 && ldhn % 4 == 0 && aligned16(p, h, h_new))
+    hipLaunchKernelGGL((gru_nonorm_fwd_kernel<true>), dim3(act_grid((long)M * (De / 4))), dim3(256), 0, s, p, ldp, h, ldh,
+                       h_new, ldhn, M, De, nb);
+  else
+    hipLaunchKernelGGL((gru_nonorm_fwd_kernel<false>), dim3(act_grid((long)M * De)), dim3(256), 0, s, p, ldp, h, ldh,
+                       h_new, ldhn, M, De, nb);
+  return (int)hipGetLastError();
+}
+
+extern "C" int dv3_gru_nonorm_fwd(const float* p, long ldp, const float* h, long ldh, float* h_new, long ldhn, int M,
+                                  int De, void* stream) {
+  return gru_nonorm_fwd_impl(p, ldp, h, ldh, h_new, ldhn, M, De, NextBlend{nullptr, nullptr, nullptr, 0}, stream);
+}
+
+extern "C" int dv3_gru_nonorm_fwd_blend(const float* p, long ldp, const float* h, long ldh, float* h_new, long ldhn,
+                                        int M, int De, const float* next_first, const float* init, float* next_out,
+                                        long ld_next, void* stream) {
+  if (!next_first || !init || !next_out || ld_next < De || ld_next % 4 != 0) return DV3_ERR_ARG;
+  if (!((De % 256 == 0 && De <= 1024) || (De % 1024 == 0 && De <= 4096))) return DV3_ERR_ARG;  // as dv3_gru_fwd_blend
+  return gru_nonorm_fwd_impl(p, ldp, h, ldh, h_new, ldhn, M, De, NextBlend{next_first, init, next_out, ld_next}, stream);
+}
+
+extern "C" int dv3_gru_nonorm_bwd(const float* dh_new, long lddhn, const float* p, long ldp, const float* h, long ldh,
+                                  float* dp, long lddp, float* dh, long lddh, int M, int De, int accumulate_dh,
+                                  void* stream) {
+  if (M <= 0) return 0;
+  if (De <= 0 || !dh_new || !p || !h || !dp || !dh || lddhn < De || ldp < 3L * De || ldh < De || lddp < 3L * De ||
+      lddh < De)
+    return DV3_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  if (De % 4 == 0 && lddhn % 4 == 0 && ldp % 4 == 0 && ldh % 4 == 0 && lddp % 4 == 0 && lddh % 4 == 0 &&
+      aligned16(dh_new, p, h, dp, dh))
+    hipLaunchKernelGGL((gru_nonorm_bwd_kernel<true>), dim3(act_grid((long)M * (De / 4))), dim3(256), 0, s, dh_new, lddhn, p,
+                       ldp, h, ldh, dp, lddp, dh, lddh, M, De, accumulate_dh);
+  else
+    hipLaunchKernelGGL((gru_nonorm_bwd_kernel<false>), dim3(act_grid((long)M * De)), dim3(256), 0, s, dh_new, lddhn, p, ldp,
+                       h, ldh, dp, lddp, dh, lddh, M, De, accumulate_dh);
+  return (int)hipGetLastError();
+}
+
 // dst = s0 | s1 | ... | s5 (flat, float): the acting step's outputs packed in one launch for a single D2H hop
 struct Concat6 {
   const float* src[6];

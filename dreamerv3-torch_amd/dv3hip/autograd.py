@@ -100,7 +100,9 @@ class LinearFn(Function):
 class TrunkFn(Function):
     """n x [Linear(no bias) -> LayerNorm(eps 1e-3) -> act] (networks.MLP.layers, networks.py:624-635; the RSSM's
     `_img_in_layers` / `_img_out_layers` / `_obs_out_layers`, networks.py:44-78) through engine.MLPEngine.
-    act: the layers' activation code (ops.ACT_CODES); params = (W0, g0, b0, W1, g1, b1, ...)."""
+    act: the layers' activation code (ops.ACT_CODES); params = (W0, g0, b0, W1, g1, b1, ...), with g = b = None for a
+    layer built with norm=False (Linear -> act; it gets no gradient for them).  The conv Functions below take their
+    layers the same way."""
 
     @staticmethod
     def forward(ctx, x, act, *params):
@@ -130,7 +132,8 @@ class TrunkFn(Function):
 
 
 class GRUFn(Function):
-    """networks.GRUCell.forward (networks.py:760-768): LN(Linear(cat[x, h])) -> gates -> h'."""
+    """networks.GRUCell.forward (networks.py:760-768): LN(Linear(cat[x, h])) -> gates -> h'.  g = b = None: a cell built
+    with norm=False, the gates on the raw Linear output."""
 
     @staticmethod
     def forward(ctx, x, h, W, g, b):
@@ -139,8 +142,12 @@ class GRUFn(Function):
         pre = torch.empty(M, 3 * De, device=x.device, dtype=F32)
         ops.gemm(x2, W.detach(), pre, A2=h2)
         out = torch.empty_like(h2)
-        mean, rstd = torch.empty(M, device=x.device), torch.empty(M, device=x.device)
-        ops.gru_fwd(pre, g.detach().contiguous(), b.detach().contiguous(), h2, out, mean, rstd)
+        mean = rstd = None
+        if g is None:
+            ops.gru_nonorm_fwd(pre, h2, out)
+        else:
+            mean, rstd = torch.empty(M, device=x.device), torch.empty(M, device=x.device)
+            ops.gru_fwd(pre, g.detach().contiguous(), b.detach().contiguous(), h2, out, mean, rstd)
         ctx.save_for_backward(x2, h2, W, g, b, pre, mean, rstd)
         return out.view(h.shape)
 
@@ -153,10 +160,13 @@ class GRUFn(Function):
         wg = any(ctx.needs_input_grad[2:])
         dpre = torch.empty_like(pre)
         dh = torch.empty_like(h2)
-        dg = torch.zeros_like(g) if wg else None
-        db = torch.zeros_like(b) if wg else None
-        ops.gru_bwd(_c(dout.reshape(M, De)), pre, g.detach().contiguous(), b.detach().contiguous(), h2, mean, rstd, dpre,
-                    dh, dg, db)
+        dg = torch.zeros_like(g) if wg and g is not None else None
+        db = torch.zeros_like(b) if wg and g is not None else None
+        if g is None:
+            ops.gru_nonorm_bwd(_c(dout.reshape(M, De)), pre, h2, dpre, dh)
+        else:
+            ops.gru_bwd(_c(dout.reshape(M, De)), pre, g.detach().contiguous(), b.detach().contiguous(), h2, mean, rstd,
+                        dpre, dh, dg, db)
         Wd = W.detach()
         dx = None
         if ctx.needs_input_grad[0]:

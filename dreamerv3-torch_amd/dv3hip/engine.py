@@ -444,8 +444,8 @@ class PLin:
 @dataclass
 class PDenseLN:
     W: torch.Tensor
-    g: torch.Tensor
-    b: torch.Tensor
+    g: Optional[torch.Tensor] = None  # LayerNorm scale / shift; None: a layer built with norm=False, act(W x)
+    b: Optional[torch.Tensor] = None
     act: int = 1  # activation code behind the LayerNorm (ops.ACT_CODES; 1 = SiLU)
 
 
@@ -475,17 +475,61 @@ def v2(t: torch.Tensor, cols: int) -> torch.Tensor:
     return t.reshape(-1, cols)
 
 
+def v1(t: Optional[torch.Tensor], n: int) -> Optional[torch.Tensor]:
+    """Row statistics as a flat [n] view (None for a layer without a LayerNorm)."""
+    return None if t is None else t.view(n)
+
+
 # ---------------------------------------------------------------------------------------------
 # Linear(no bias) -> LN -> SiLU on row blocks
 # ---------------------------------------------------------------------------------------------
+# A layer built with norm=False (networks.py:53-78, 627-633: the LayerNorm module is left out, nothing else changes) has
+# g = b = None: its row kernel is the activation alone, it keeps no mean / rstd, and the fusions whose kernel contains
+# a LayerNorm are off for THAT layer -- its neighbours with a LayerNorm keep theirs.
+def ln_fwd(L, pre, y, mean=None, rstd=None, *, chw_group=0):
+    """y = act(LN(pre)) of layer L (PDenseLN / PConvLayer), or act(pre) for a layer without a LayerNorm."""
+    if L.g is None:
+        ops.act_fwd(pre, y, act=L.act, chw_group=chw_group)
+    else:
+        ops.ln_act_fwd(pre, L.g, L.b, y, mean, rstd, act=L.act, chw_group=chw_group)
+
+
+def ln_bwd(L, dy, pre, mean, rstd, dpre, *, wgrad: bool, chw_group=0):
+    """dpre from dy = d / d act(LN(pre)); with wgrad the LayerNorm's parameter gradients are accumulated."""
+    if L.g is None:
+        ops.act_bwd(dy, pre, dpre, act=L.act, chw_group=chw_group)
+    else:
+        ops.ln_act_bwd(dy, pre, L.g, L.b, mean, rstd, dpre, _g(L.g) if wgrad else None, _g(L.b) if wgrad else None,
+                       act=L.act, chw_group=chw_group)
+
+
+def _sl(t, s):
+    """t[s], or None for the statistics a layer without a LayerNorm does not keep."""
+    return None if t is None else t[s]
+
+
 def dense_ln_fwd(L: PDenseLN, x1, x2, pre, mean, rstd, y, *, accumulate_pre=False):
     ops.gemm(x1, L.W, pre, A2=x2, accumulate=accumulate_pre)
-    ops.ln_act_fwd(pre, L.g, L.b, y, mean, rstd, act=L.act)
+    ln_fwd(L, pre, y, mean, rstd)
 
 
 def dense_ln_bwd_pre(L: PDenseLN, dy, pre, mean, rstd, dpre, *, wgrad: bool):
-    ops.ln_act_bwd(dy, pre, L.g, L.b, mean, rstd, dpre, _g(L.g) if wgrad else None, _g(L.b) if wgrad else None,
-                   act=L.act)
+    ln_bwd(L, dy, pre, mean, rstd, dpre, wgrad=wgrad)
+
+
+def gru_gates_fwd(L: PDenseLN, p, h, h_new, mean, rstd, *, next_blend=None):
+    if L.g is None:
+        ops.gru_nonorm_fwd(p, h, h_new, next_blend=next_blend)
+    else:
+        ops.gru_fwd(p, L.g, L.b, h, h_new, mean, rstd, next_blend=next_blend)
+
+
+def gru_gates_bwd(L: PDenseLN, dh_new, p, h, mean, rstd, dp, dh, *, wgrad: bool, accumulate_dh=False):
+    if L.g is None:
+        ops.gru_nonorm_bwd(dh_new, p, h, dp, dh, accumulate_dh=accumulate_dh)
+    else:
+        ops.gru_bwd(dh_new, p, L.g, L.b, h, mean, rstd, dp, dh, _g(L.g) if wgrad else None, _g(L.b) if wgrad else None,
+                    accumulate_dh=accumulate_dh)
 
 
 def lin_wgrad(W, dY, x1, x2=None):
@@ -534,8 +578,9 @@ class MLPEngine:
         acts = []
         for i, L in enumerate(P.layers):
             U = L.W.shape[0]
-            acts.append((ws.get(f"{nm}.pre{i}", (total, U)), ws.get(f"{nm}.m{i}", (total,)),
-                         ws.get(f"{nm}.r{i}", (total,)), ws.get(f"{nm}.y{i}", (total, U))))
+            ln = L.g is not None
+            acts.append((ws.get(f"{nm}.pre{i}", (total, U)), ws.get(f"{nm}.m{i}", (total,)) if ln else None,
+                         ws.get(f"{nm}.r{i}", (total,)) if ln else None, ws.get(f"{nm}.y{i}", (total, U))))
         out = ws.get(f"{nm}.out", (total, P.out.W.shape[0])) if P.out is not None else None
         out2 = ws.get(f"{nm}.out2", (total, P.out2.W.shape[0])) if P.out2 is not None else None
         return acts, out, out2
@@ -561,7 +606,8 @@ class MLPEngine:
         weight columns of every row (pack_onehot must have run), fused with its LayerNorm + SiLU.
         head (dict, actor only): run the last layer's LayerNorm + SiLU, both head Linears, the action sample and
         the entropy as ONE launch (ops.actor_head); keys: action, ent, noise, rng, eps_out, onehot, min_std,
-        max_std, unimix, act_idx, forced, flips.
+        max_std, unimix, act_idx, forced, flips.  A last layer without a LayerNorm has no such launch: its activation,
+        the head GEMMs and the sampler run one after the other (_head_unfused).
         base0 ([R, U], with idx): x2 @ W0[:, SD:]^T computed elsewhere (RSSMEngine.img_step_fwd's stacked GEMM)."""
         P = self.P
         R = x1.shape[0]
@@ -570,8 +616,9 @@ class MLPEngine:
         rs = slice(row0, row0 + R)
         h1, h2 = x1, x2
         n_layers = len(P.layers)
+        fused_head = head is not None and P.layers[-1].g is not None
         for i, ((pre, mean, rstd, y), L) in enumerate(zip(acts, P.layers)):
-            last_fused = head is not None and i == n_layers - 1
+            last_fused = fused_head and i == n_layers - 1
             if i == 0 and idx is not None:
                 SD = idx.shape[1] * D
                 wt = self.ws.get(f"{self.name}.wt0", (SD, L.W.shape[0]))
@@ -581,14 +628,19 @@ class MLPEngine:
                     base = pre[rs]
                 if last_fused:
                     ops.onehot_linear_ln(idx, D, wt, pre[rs], base=base)
+                elif L.g is None:  # the gather writes the pre-activations, the activation is a launch of its own
+                    ops.onehot_linear_ln(idx, D, wt, pre[rs], base=base)
+                    ln_fwd(L, pre[rs], y[rs])
                 else:
                     ops.onehot_linear_ln(idx, D, wt, pre[rs], base=base, gamma=L.g, beta=L.b, y=y[rs], mean=mean[rs],
                                          rstd=rstd[rs], act=L.act)
             elif last_fused:
                 ops.gemm(h1, L.W, pre[rs], A2=h2)
             else:
-                dense_ln_fwd(L, h1, h2, pre[rs], mean[rs], rstd[rs], y[rs])
+                dense_ln_fwd(L, h1, h2, pre[rs], _sl(mean, rs), _sl(rstd, rs), y[rs])
             h1, h2 = y[rs], None
+        if head is not None and not fused_head:
+            return self._head_unfused(h1, out[rs], None if head.get("onehot") else out2[rs], head)
         if head is not None:
             pre, mean, rstd, y = acts[-1]
             L = P.layers[-1]
@@ -609,6 +661,31 @@ class MLPEngine:
             o2 = out2[rs]
             ops.gemm(h1, P.out2.W, o2, bias=P.out2.b)
         return h1, o, o2
+
+    def _head_unfused(self, h, o, o2, head):
+        """What ops.actor_head does behind the last layer's row kernel, launch by launch: the head Linears, then the
+        action sample and its entropy (the sequence of the rollout without fused launches, models.ImagBehavior)."""
+        P = self.P
+        ops.gemm(h, P.out.W, o, bias=P.out.b)
+        noise, rng = head.get("noise"), head.get("rng")
+        if head.get("onehot", False):
+            unimix = head.get("unimix", 0.01)
+            act_idx = head.get("act_idx")
+            ops.onehot_sample(o, head["action"], noise=noise, rng=rng, unimix=unimix, forced=head.get("forced"),
+                              flips=head.get("flips"), idx=None if act_idx is None else act_idx.view(-1))
+            ops.onehot_ent_logp_fwd(o, None, head["ent"], None, unimix=unimix)
+            return h, o, None
+        ops.gemm(h, P.out2.W, o2, bias=P.out2.b)
+        eps = head.get("eps_out")
+        if eps is None:
+            eps = self.ws.get(f"{self.name}.eps", tuple(o.shape))
+        if noise is not None:
+            eps.copy_(noise.view(eps.shape))
+        else:
+            ops.fill_normal(eps, rng)
+        ops.actor_normal_fwd(o, o2, eps, head["action"], head["ent"], min_std=head.get("min_std", 0.1),
+                             max_std=head.get("max_std", 1.0))
+        return h, o, o2
 
     def backward(self, x1, x2, rows: slice, dout=None, dout2=None, *, wgrad: bool, dx1=None, dx2=None,
                  acc_dx=False, dh=None, defer=None, idx=None, D=0):
@@ -647,7 +724,7 @@ class MLPEngine:
             pre, mean, rstd, _ = acts[i]
             xin1, xin2 = (acts[i - 1][3][rows], None) if i > 0 else (x1, x2)
             dpre = ws.get(f"{nm}.dpre{i}", (R, pre.shape[1]))
-            dense_ln_bwd_pre(L, dy, pre[rows], mean[rows], rstd[rows], dpre, wgrad=wgrad)
+            dense_ln_bwd_pre(L, dy, pre[rows], _sl(mean, rows), _sl(rstd, rows), dpre, wgrad=wgrad)
             if wgrad:
                 def _wg(L=L, dpre=dpre, xin1=xin1, xin2=xin2, i=i):
                     if i == 0 and idx is not None:
@@ -696,6 +773,12 @@ class RSSMEngine:
         self.head = dict(mean_act=mean_act, std_act=std_act, min_std=float(min_std))
         self.head_bwd = dict(mean_act=mean_act, std_act=std_act)
 
+    def _stats(self, L, mean_name, rstd_name, shape):
+        """The mean / rstd buffers of layer L's LayerNorm, or (None, None) for a layer that has none."""
+        if L.g is None:
+            return None, None
+        return self.ws.get(mean_name, shape), self.ws.get(rstd_name, shape)
+
     # -- initial state (networks.py:99-123, 235-239): deter0 = tanh(W), stoch0 = mode(prior head) -----
     def init_state_fwd(self):
         P, ws = self.P, self.ws
@@ -703,7 +786,7 @@ class RSSMEngine:
         ops.tanh_fwd(P.W0, d0)
         x0pre = ws.get("init.x0pre", (1, self.Hd))
         x0 = ws.get("init.x0", (1, self.Hd))
-        m0, r0 = ws.get("init.m", (1,)), ws.get("init.r", (1,))
+        m0, r0 = self._stats(P.img_out, "init.m", "init.r", (1,))
         dense_ln_fwd(P.img_out, d0, None, x0pre, m0, r0, x0)
         l0 = ws.get("init.logit", (1, self.SW))
         ops.gemm(x0, P.ims.W, l0, bias=P.ims.b)
@@ -720,7 +803,7 @@ class RSSMEngine:
         P, ws = self.P, self.ws
         l0, x0, x0pre, d0 = ws.get("init.logit", (1, self.SW)), ws.get("init.x0", (1, self.Hd)), \
             ws.get("init.x0pre", (1, self.Hd)), ws.get("init.deter", (1, self.De))
-        m0, r0 = ws.get("init.m", (1,)), ws.get("init.r", (1,))
+        m0, r0 = self._stats(P.img_out, "init.m", "init.r", (1,))
         dl0 = ws.get("init.dlogit", (1, self.SW))
         if self.gauss:
             ops.gauss_head_bwd(l0, dl0, dstoch=dstoch0.view(1, self.S), mode=True, **self.head_bwd)
@@ -745,13 +828,14 @@ class RSSMEngine:
         step inputs), x1pre/x1/m1/r1 (img_in), gpre/mg/rg (GRU), deter, x3pre/x3/m3/r3 (obs_out), x2pre/x2/m2/r2
         (img_out, batched)."""
         T, B, SD, De, Hd, A = self.T, self.B, self.SD, self.De, self.Hd, self.A
-        g = self.ws.get
+        g, P = self.ws.get, self.P
+        # (the statistics of a layer without a LayerNorm are None: no buffer, and nothing reads them)
         return (g("obs.first", (T, B)), g("obs.sin", (T, B, SD)), g("obs.din", (T, B, De)), g("obs.ain", (T, B, A)),
-                g("obs.x1pre", (T, B, Hd)), g("obs.x1", (T, B, Hd)), g("obs.m1", (T, B)), g("obs.r1", (T, B)),
-                g("obs.gpre", (T, B, 3 * De)), g("obs.mg", (T, B)), g("obs.rg", (T, B)),
+                g("obs.x1pre", (T, B, Hd)), g("obs.x1", (T, B, Hd)), *self._stats(P.img_in, "obs.m1", "obs.r1", (T, B)),
+                g("obs.gpre", (T, B, 3 * De)), *self._stats(P.gru, "obs.mg", "obs.rg", (T, B)),
                 g("obs.deter", (T, B, De)),
-                g("obs.x3pre", (T, B, Hd)), g("obs.x3", (T, B, Hd)), g("obs.m3", (T, B)), g("obs.r3", (T, B)),
-                g("obs.x2pre", (T, B, Hd)), g("obs.x2", (T, B, Hd)), g("obs.m2", (T, B)), g("obs.r2", (T, B)))
+                g("obs.x3pre", (T, B, Hd)), g("obs.x3", (T, B, Hd)), *self._stats(P.obs_out, "obs.m3", "obs.r3", (T, B)),
+                g("obs.x2pre", (T, B, Hd)), g("obs.x2", (T, B, Hd)), *self._stats(P.img_out, "obs.m2", "obs.r2", (T, B)))
 
     def observe_fwd(self, embed_tm, action_tm, first_tm, *, q_prior=None, q_post=None, rng=None, force=None,
                     state0=None):
@@ -820,8 +904,11 @@ class RSSMEngine:
         ops.reset_blend(v2(action_tm, A), None, first.view(TB), v2(ain, A))
         fuse = ((De % 256 == 0 and De <= 1024) or (De % 1024 == 0 and De <= 4096)) and _FUSE_BLEND
         # (the sample + img_in launch is SiLU-only: another activation keeps the sample and the gather as two launches)
-        fuse_in = fuse and gather and _FUSE_SAMPLE_IN and ops.sample_linear_ln_ok(S, D, Hd, P.img_in.act) and Hd % 4 == 0
-        fuse_row = _FUSE_SCAN_ROW and _FUSE_SCAN_LN and B <= 64 and ops.scan_ln_gemm_ok(Hd, SW)
+        # (both launches contain a LayerNorm: the one of img_in / of obs_out -- a layer built without one keeps its own launches)
+        fuse_in = (fuse and gather and _FUSE_SAMPLE_IN and ops.sample_linear_ln_ok(S, D, Hd, P.img_in.act) and Hd % 4 == 0
+                   and P.img_in.g is not None)
+        fuse_row = (_FUSE_SCAN_ROW and _FUSE_SCAN_LN and B <= 64 and ops.scan_ln_gemm_ok(Hd, SW)
+                    and P.obs_out.g is not None)
         Cuts.mark("wm.fscan")  # (pipelined capture: the forward scan is a lane segment of its own)
         for t in range(T):
             if T >= 16 and t == (3 * T) // 4:
@@ -835,20 +922,23 @@ class RSSMEngine:
             nxt = fuse and t + 1 < T
             if fuse_in and t > 0:
                 pass  # x1[t] came out of step t-1's fused sample + img_in launch
+            elif gather and P.img_in.g is None:  # the gather writes the pre-activations; the activation follows
+                ops.onehot_linear_ln(idx_in[t], D, wt_in, x1pre[t], x2=ain[t])
+                ln_fwd(P.img_in, x1pre[t], x1[t])
             elif gather:
                 ops.onehot_linear_ln(idx_in[t], D, wt_in, x1pre[t], x2=ain[t], gamma=P.img_in.g, beta=P.img_in.b,
                                      y=x1[t], mean=m1[t], rstd=r1[t], act=P.img_in.act)
             else:
-                dense_ln_fwd(P.img_in, sin[t], ain[t], x1pre[t], m1[t], r1[t], x1[t])
+                dense_ln_fwd(P.img_in, sin[t], ain[t], x1pre[t], _sl(m1, t), _sl(r1, t), x1[t])
             ops.gemm(x1[t], P.gru.W, gpre[t], A2=din[t])
-            ops.gru_fwd(gpre[t], P.gru.g, P.gru.b, din[t], deter[t], mg[t], rg[t],
-                        next_blend=(first[t + 1], d0.view(De), din[t + 1]) if nxt else None)
+            gru_gates_fwd(P.gru, gpre[t], din[t], deter[t], _sl(mg, t), _sl(rg, t),
+                          next_blend=(first[t + 1], d0.view(De), din[t + 1]) if nxt else None)
             ops.gemm(deter[t], P.obs_out.W[:, :De], x3pre[t], accumulate=True)
             if fuse_row:  # the obs_out LayerNorm rides in the stat GEMM (5 launches per step instead of 6)
                 ops.scan_ln_gemm(x3pre[t], P.obs_out.g, P.obs_out.b, x3[t], m3[t], r3[t], P.obs.W,
                                  post_stat[t].view(B, SW), bias=P.obs.b, act=P.obs_out.act)
             else:
-                ops.ln_act_fwd(x3pre[t], P.obs_out.g, P.obs_out.b, x3[t], m3[t], r3[t], act=P.obs_out.act)
+                ln_fwd(P.obs_out, x3pre[t], x3[t], _sl(m3, t), _sl(r3, t))
                 ops.gemm(x3[t], P.obs.W, post_stat[t].view(B, SW), bias=P.obs.b)
             if gauss:
                 ops.gauss_head_fwd(post_stat[t], post_stoch[t], post_mean[t], post_std[t],
@@ -872,7 +962,7 @@ class RSSMEngine:
                                   forced=None if f_post is None else f_post[t], flips=flips, idx=post_idx[t].view(-1))
         Cuts.mark("wm.mid")
         # prior head for all steps at once
-        dense_ln_fwd(P.img_out, v2(deter, De), None, v2(x2pre, Hd), m2.view(TB), r2.view(TB), v2(x2, Hd))
+        dense_ln_fwd(P.img_out, v2(deter, De), None, v2(x2pre, Hd), v1(m2, TB), v1(r2, TB), v2(x2, Hd))
         ops.gemm(v2(x2, Hd), P.ims.W, v2(prior_stat, SW), bias=P.ims.b)
         self._embed = embed_tm
         if gauss:
@@ -944,7 +1034,7 @@ class RSSMEngine:
         side = SideStream(dprior_logit.device, lanes_pay=lanes_pay)
         ops.gemm(dpl2, P.ims.W, dx2, transB=False)
         dx2pre = g("obs.dx2pre", (TB, Hd))
-        dense_ln_bwd_pre(P.img_out, dx2, v2(x2pre, Hd), m2.view(TB), r2.view(TB), dx2pre, wgrad=True)
+        dense_ln_bwd_pre(P.img_out, dx2, v2(x2pre, Hd), v1(m2, TB), v1(r2, TB), dx2pre, wgrad=True)
         ops.gemm(dx2pre, P.img_out.W, v2(gd, De), transB=False, accumulate=True)
 
         def _prior_wgrads():
@@ -970,7 +1060,7 @@ class RSSMEngine:
             fuse_carry = _FUSE_CARRY and not gauss  # (the fused carry launches end in the one-hot straight-through)
             # row operations in the prologue of the few-row GEMM that consumes them (csrc/scanops.hip): 5 launches per step
             fuse_row = (_FUSE_SCAN_ROW and _FUSE_SCAN_LNBWD and B <= 64 and ops.scan_lnbwd_gemm_ok(Hd, De)
-                        and ops.scan_lnbwd_gemm_ok(Hd, SD))
+                        and ops.scan_lnbwd_gemm_ok(Hd, SD) and P.obs_out.g is not None and P.img_in.g is not None)
             fuse_cs = (_FUSE_SCAN_ROW and _FUSE_SCAN_CS and B <= 64 and fuse_carry and ops.scan_carry_st_gemm_ok(S, D, Hd))
             # (the fused first launch re-reads its inputs from every column tile: the finished logit gradient goes to its
             # own buffer instead of in place)
@@ -981,7 +1071,7 @@ class RSSMEngine:
             # (measured, world-model update: cfg 2 (De 512, 16 rows) 10.30 -> 10.15 ms; cfg 3 (De 1024, 32 rows) 17.19 -> 17.48:
             # 288 workgroups x 2 row blocks each re-reading 192 KB of factors -- the wide cell keeps its own launch)
             fuse_gru = (_FUSE_SCAN_ROW and _FUSE_SCAN_GRUBWD and B <= 32 and De <= 512
-                        and ops.scan_grubwd_gemm_ok(De, Hd + De))
+                        and ops.scan_grubwd_gemm_ok(De, Hd + De) and P.gru.g is not None)
             if fuse_gru:
                 # ... and the GRU cell's backward: every transcendental factor for all steps in one launch
                 xhg, afg = g("obs.xhg", (T, B, 3 * De)), g("obs.afg", (T, B, 3 * De))
@@ -1025,20 +1115,19 @@ class RSSMEngine:
                     ops.scan_lnbwd_gemm(dx3[t], xh3[t], jc3[t], P.obs_out.g, r3[t], dx3pre[t], P.obs_out.W[:, :De], gd_t,
                                         _g(P.obs_out.g), _g(P.obs_out.b))
                 else:
-                    dense_ln_bwd_pre(P.obs_out, dx3[t], x3pre[t], m3[t], r3[t], dx3pre[t], wgrad=True)
+                    dense_ln_bwd_pre(P.obs_out, dx3[t], x3pre[t], _sl(m3, t), _sl(r3, t), dx3pre[t], wgrad=True)
                     ops.gemm(dx3pre[t], P.obs_out.W[:, :De], gd_t, transB=False, accumulate="atomic")
                 if fuse_gru:
                     ops.scan_grubwd_gemm(gd_t, xhg[t], afg[t], p1g[t], p2g[t], ahg[t], P.gru.g, rg[t], dgpre[t], ddin, P.gru.W,
                                          dxd[t], _g(P.gru.g), _g(P.gru.b))
                 else:
-                    ops.gru_bwd(gd_t, gpre[t], P.gru.g, P.gru.b, din[t], mg[t], rg[t], dgpre[t], ddin, _g(P.gru.g),
-                                _g(P.gru.b))
+                    gru_gates_bwd(P.gru, gd_t, gpre[t], din[t], _sl(mg, t), _sl(rg, t), dgpre[t], ddin, wgrad=True)
                     ops.gemm(dgpre[t], P.gru.W, dxd[t], transB=False, accumulate="atomic")
                 if fuse_row:
                     ops.scan_lnbwd_gemm(dx1, xh1[t], jc1[t], P.img_in.g, r1[t], dx1pre[t], P.img_in.W[:, :SD], dsin[t],
                                         _g(P.img_in.g), _g(P.img_in.b))
                 else:
-                    dense_ln_bwd_pre(P.img_in, dx1, x1pre[t], m1[t], r1[t], dx1pre[t], wgrad=True)
+                    dense_ln_bwd_pre(P.img_in, dx1, x1pre[t], _sl(m1, t), _sl(r1, t), dx1pre[t], wgrad=True)
                     ops.gemm(dx1pre[t], P.img_in.W[:, :SD], dsin[t], transB=False, accumulate="atomic")
                 if fuse_cs:
                     if t == 0:
@@ -1092,14 +1181,19 @@ class RSSMEngine:
         head=False stops after the GRU (deter' only): the acting step never reads the prior (dreamer.py:131-134)."""
         P = self.P
         M = stoch.shape[0]
+        # (bufs holds m1/r1, mg/rg, m2/r2 only for the layers that have a LayerNorm)
         if idx is not None:
             wt = self.ws.get("rssm.img_in_wt", (P.img_in.W.shape[1], P.img_in.W.shape[0]))
-            ops.onehot_linear_ln(idx, self.D, wt, bufs["x1pre"], x2=action, gamma=P.img_in.g, beta=P.img_in.b,
-                                 y=bufs["x1"], mean=bufs["m1"], rstd=bufs["r1"], act=P.img_in.act)
+            if P.img_in.g is None:
+                ops.onehot_linear_ln(idx, self.D, wt, bufs["x1pre"], x2=action)
+                ln_fwd(P.img_in, bufs["x1pre"], bufs["x1"])
+            else:
+                ops.onehot_linear_ln(idx, self.D, wt, bufs["x1pre"], x2=action, gamma=P.img_in.g, beta=P.img_in.b,
+                                     y=bufs["x1"], mean=bufs["m1"], rstd=bufs["r1"], act=P.img_in.act)
         else:
-            dense_ln_fwd(P.img_in, stoch, action, bufs["x1pre"], bufs["m1"], bufs["r1"], bufs["x1"])
+            dense_ln_fwd(P.img_in, stoch, action, bufs["x1pre"], bufs.get("m1"), bufs.get("r1"), bufs["x1"])
         ops.gemm(bufs["x1"], P.gru.W, bufs["gpre"], A2=deter)
-        ops.gru_fwd(bufs["gpre"], P.gru.g, P.gru.b, deter, bufs["deter"], bufs["mg"], bufs["rg"])
+        gru_gates_fwd(P.gru, bufs["gpre"], deter, bufs["deter"], bufs.get("mg"), bufs.get("rg"))
         if not head:
             return
         fuse_smp = _FUSE_SAMPLE and not self.gauss and ops.gemm_sample_ok(M, self.SD, self.D)
@@ -1107,7 +1201,7 @@ class RSSMEngine:
             ops.gemm(bufs["deter"], wcat, bufs["cat"])
         else:
             ops.gemm(bufs["deter"], P.img_out.W, bufs["x2pre"])
-        ops.ln_act_fwd(bufs["x2pre"], P.img_out.g, P.img_out.b, bufs["x2"], bufs["m2"], bufs["r2"], act=P.img_out.act)
+        ln_fwd(P.img_out, bufs["x2pre"], bufs["x2"], bufs.get("m2"), bufs.get("r2"))
         if self.gauss:
             # bufs: raw [M,2S], mean / std / stoch / eps [M,S]; noise: N(0,1) draws [M,S]
             ops.gemm(bufs["x2"], P.ims.W, bufs["raw"], bias=P.ims.b)
@@ -1155,18 +1249,18 @@ class RSSMEngine:
             ops.onehot_st_bwd(bufs["logit"], dstoch.view(M, S, D), dlogit.view(M, S, D), unimix=self.unimix)
         if wt is not None:  # transposed weights (pack_bwd): every data gradient in the y = x B^T form
             ops.gemm(dlogit, wt["ims"], scratch["dx2"])
-            dense_ln_bwd_pre(P.img_out, scratch["dx2"], bufs["x2pre"], bufs["m2"], bufs["r2"], scratch["dx2pre"],
+            dense_ln_bwd_pre(P.img_out, scratch["dx2"], bufs["x2pre"], bufs.get("m2"), bufs.get("r2"), scratch["dx2pre"],
                              wgrad=False)
             ops.gemm(scratch["dx2pre"], wt["out"], ddeter, accumulate=True)
-            ops.gru_bwd(ddeter, bufs["gpre"], P.gru.g, P.gru.b, prev_deter, bufs["mg"], bufs["rg"], scratch["dgpre"],
-                        dprev_deter, accumulate_dh=accumulate_prev)
+            gru_gates_bwd(P.gru, ddeter, bufs["gpre"], prev_deter, bufs.get("mg"), bufs.get("rg"), scratch["dgpre"],
+                          dprev_deter, wgrad=False, accumulate_dh=accumulate_prev)
             if M > 128 and ops.gemm_split_ok(scratch["dgpre"], wt["gru"]):
                 # [dx1 | dh] = dgpre W_gru in one launch, dh accumulating onto the direct path gru_bwd just wrote
                 ops.gemm_split(scratch["dgpre"], wt["gru"], scratch["dx1"], dprev_deter, accumulate2=True)
             else:
                 ops.gemm(scratch["dgpre"], wt["gru"][Hd:], dprev_deter, accumulate=True)
                 ops.gemm(scratch["dgpre"], wt["gru"][:Hd], scratch["dx1"])
-            dense_ln_bwd_pre(P.img_in, scratch["dx1"], bufs["x1pre"], bufs["m1"], bufs["r1"], scratch["dx1pre"],
+            dense_ln_bwd_pre(P.img_in, scratch["dx1"], bufs["x1pre"], bufs.get("m1"), bufs.get("r1"), scratch["dx1pre"],
                              wgrad=False)
             if daction is not None and M > 128 and SD % 16 == 0 and ops.gemm_split_ok(scratch["dx1pre"], wt["in"]):
                 # [dstoch | daction] = dx1pre W_in in one launch (the action's few columns ride in the last column tile)
@@ -1177,14 +1271,14 @@ class RSSMEngine:
                 ops.gemm(scratch["dx1pre"], wt["in"][SD:], daction)
             return
         ops.gemm(dlogit, P.ims.W, scratch["dx2"], transB=False)
-        dense_ln_bwd_pre(P.img_out, scratch["dx2"], bufs["x2pre"], bufs["m2"], bufs["r2"], scratch["dx2pre"],
+        dense_ln_bwd_pre(P.img_out, scratch["dx2"], bufs["x2pre"], bufs.get("m2"), bufs.get("r2"), scratch["dx2pre"],
                          wgrad=False)
         ops.gemm(scratch["dx2pre"], P.img_out.W, ddeter, transB=False, accumulate=True)
-        ops.gru_bwd(ddeter, bufs["gpre"], P.gru.g, P.gru.b, prev_deter, bufs["mg"], bufs["rg"], scratch["dgpre"],
-                    dprev_deter, accumulate_dh=accumulate_prev)
+        gru_gates_bwd(P.gru, ddeter, bufs["gpre"], prev_deter, bufs.get("mg"), bufs.get("rg"), scratch["dgpre"],
+                      dprev_deter, wgrad=False, accumulate_dh=accumulate_prev)
         ops.gemm(scratch["dgpre"], P.gru.W[:, Hd:], dprev_deter, transB=False, accumulate=True)
         ops.gemm(scratch["dgpre"], P.gru.W[:, :Hd], scratch["dx1"], transB=False)
-        dense_ln_bwd_pre(P.img_in, scratch["dx1"], bufs["x1pre"], bufs["m1"], bufs["r1"], scratch["dx1pre"],
+        dense_ln_bwd_pre(P.img_in, scratch["dx1"], bufs["x1pre"], bufs.get("m1"), bufs.get("r1"), scratch["dx1pre"],
                          wgrad=False)
         ops.gemm(scratch["dx1pre"], P.img_in.W[:, :SD], dprev_stoch, transB=False, accumulate=accumulate_prev)
         if daction is not None:
@@ -1197,10 +1291,15 @@ class RSSMEngine:
 @dataclass
 class PConvLayer:
     W: torch.Tensor  # Conv2d [Co,Ci,4,4] (encoder) / ConvTranspose2d [Ci,Co,4,4] (decoder)
-    g: Optional[torch.Tensor] = None  # channel LayerNorm scale / shift (None on the decoder's last layer)
-    b: Optional[torch.Tensor] = None
+    g: Optional[torch.Tensor] = None  # channel LayerNorm scale / shift (None on the decoder's last layer, and on
+    b: Optional[torch.Tensor] = None  # every layer of a stack built with norm=False: conv -> act)
     bias: Optional[torch.Tensor] = None  # only the decoder's last layer has a bias
     act: int = 1  # activation code behind the channel LayerNorm (ops.ACT_CODES; 1 = SiLU)
+    out: bool = False  # the decoder's last layer: no LayerNorm and no activation in either mode (networks.py:529-548)
+
+    def __post_init__(self):
+        if self.bias is not None:  # (only that layer has a bias, with and without norm)
+            self.out = True
 
 
 # acting path: conv layers with at most this many output pixels (all images) use im2col + GEMM
@@ -1242,11 +1341,10 @@ class ConvEncoderEngine:
                 ops.pack_conv_weight(L.W, wp, transposed=False)
                 ops.conv_s2_fwd(x, wp, pre, Ci=Ci, Co=Co)
             R = N * OH * OH
-            mean, rstd = ws.get(f"enc.m{i}", (R,)), ws.get(f"enc.r{i}", (R,))
+            mean, rstd = (ws.get(f"enc.m{i}", (R,)), ws.get(f"enc.r{i}", (R,))) if L.g is not None else (None, None)
             last = i == n_layers - 1
             y = ws.get(f"enc.y{i}", (N, Co * OH * OH) if last else (N, OH, OH, Co))
-            ops.ln_act_fwd(pre.view(R, Co), L.g, L.b, y if last else y.view(R, Co), mean, rstd, act=L.act,
-                           chw_group=OH * OH if last else 0)
+            ln_fwd(L, pre.view(R, Co), y if last else y.view(R, Co), mean, rstd, chw_group=OH * OH if last else 0)
             self._acts.append((x, pre, mean, rstd, y))
             x, H = y, OH
         return x
@@ -1263,8 +1361,8 @@ class ConvEncoderEngine:
             R = N * OH * OH
             last = i == n_layers - 1
             dpre = ws.get(f"enc.dpre{i}", pre.shape)
-            ops.ln_act_bwd(dy if last else dy.view(R, Co), pre.view(R, Co), L.g, L.b, mean, rstd, dpre.view(R, Co),
-                           _g(L.g), _g(L.b), act=L.act, chw_group=OH * OH if last else 0)
+            ln_bwd(L, dy if last else dy.view(R, Co), pre.view(R, Co), mean, rstd, dpre.view(R, Co), wgrad=True,
+                   chw_group=OH * OH if last else 0)
             ops.conv_s2_wgrad(dpre, x, _g(L.W))
             if i > 0:
                 wpt = ws.get(f"enc.wpt{i}", (4, Ci, 4 * Co))
@@ -1293,17 +1391,18 @@ class ConvDecoderEngine:
         for i, L in enumerate(self.L):
             Ci, Co = L.W.shape[0], L.W.shape[1]
             OH = 2 * H
-            c3 = L.g is None and Co == 3 and Ci in ops.C3_WIDTHS
+            c3 = L.out and Co == 3 and Ci in ops.C3_WIDTHS
             if not c3:
                 wpt = ws.get(f"dec.wpt{i}", (4, Co, 4 * Ci))
                 ops.pack_conv_weight(L.W, wpt, transposed=True)
-            if L.g is not None:
+            if not L.out:
                 pre = ws.get(f"dec.pre{i}", (R, OH, OH, Co))
                 ops.convT_s2_fwd(x, wpt, pre, Ci=Ci, Co=Co)
                 rows = R * OH * OH
-                mean, rstd = ws.get(f"dec.m{i}", (rows,)), ws.get(f"dec.r{i}", (rows,))
+                mean, rstd = (ws.get(f"dec.m{i}", (rows,)), ws.get(f"dec.r{i}", (rows,))) if L.g is not None \
+                    else (None, None)
                 y = ws.get(f"dec.y{i}", (R, OH, OH, Co))
-                ops.ln_act_fwd(pre.view(rows, Co), L.g, L.b, y.view(rows, Co), mean, rstd, act=L.act)
+                ln_fwd(L, pre.view(rows, Co), y.view(rows, Co), mean, rstd)
                 self._acts.append((x, pre, mean, rstd, y))
             else:
                 y = ws.get("dec.recon", (R, OH, OH, Co))
@@ -1327,10 +1426,9 @@ class ConvDecoderEngine:
             Ci, Co = L.W.shape[0], L.W.shape[1]
             R, OH = y.shape[0], y.shape[1]
             rows = R * OH * OH
-            if L.g is not None:
+            if not L.out:
                 dpre = ws.get(f"dec.dpre{i}", pre.shape)
-                ops.ln_act_bwd(dy.view(rows, Co), pre.view(rows, Co), L.g, L.b, mean, rstd, dpre.view(rows, Co),
-                               _g(L.g), _g(L.b), act=L.act)
+                ln_bwd(L, dy.view(rows, Co), pre.view(rows, Co), mean, rstd, dpre.view(rows, Co), wgrad=True)
             else:
                 dpre = dy
                 if L.bias is not None:

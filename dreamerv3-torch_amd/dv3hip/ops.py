@@ -595,6 +595,49 @@ def _ln_partials(device):
     return t
 
 
+# grid cap of the LayerNorm-free row kernels (csrc/rowops.hip kActGridCap): workgroups of 256 threads, one 16-byte chunk
+# (or one float) per thread and trip -- more than ACT_GRID_CAP * 256 of them take a second trip of the grid-stride loop
+ACT_GRID_CAP = 2048
+
+
+def act_fwd(x, y, *, act=True, chw_group=0):
+    """y = act(x): the layer of a stack built with norm=False (ln_act_fwd without the LayerNorm, same addressing)."""
+    R, N, ldx = _rows2d(x, "x")
+    if chw_group:
+        _contig(y, "y")
+        if y.numel() != R * N or R % chw_group:
+            raise ValueError("chw output size mismatch")
+        ldy = N
+    else:
+        Ry, Ny, ldy = _rows2d(y, "y")
+        if (Ry, Ny) != (R, N):
+            raise ValueError("y shape mismatch")
+    _call("dv3_act_fwd", _ptr(x), ldx, _ptr(y), ldy, R, N, act_code(act), int(chw_group), _stream(),
+          key="dv3_act_fwd" + (f"[{R}x{N}]" if PROFILE.by_shape else ""), nbytes=8.0 * R * N)
+    return y
+
+
+def act_bwd(dy, x, dx, *, act=True, chw_group=0, accumulate_dx=False):
+    """dx (+)= dy * act'(x) (ln_act_bwd without the LayerNorm: no statistics, no parameter gradients)."""
+    R, N, ldx = _rows2d(x, "x")
+    if chw_group:
+        _contig(dy, "dy")
+        if dy.numel() != R * N or R % chw_group:
+            raise ValueError("dy size mismatch")
+        lddy = N
+    else:
+        Rd, Nd, lddy = _rows2d(dy, "dy")
+        if (Rd, Nd) != (R, N):
+            raise ValueError("dy shape mismatch")
+    Rx, Nx, lddx = _rows2d(dx, "dx")
+    if (Rx, Nx) != (R, N):
+        raise ValueError("dx shape mismatch")
+    _call("dv3_act_bwd", _ptr(dy), lddy, _ptr(x), ldx, _ptr(dx), lddx, R, N, act_code(act), int(chw_group),
+          int(accumulate_dx), _stream(), key="dv3_act_bwd" + (f"[{R}x{N}]" if PROFILE.by_shape else ""),
+          nbytes=12.0 * R * N)
+    return dx
+
+
 def gru_fwd(p, gamma, beta, h, h_new, mean, rstd, *, next_blend=None):
     """next_blend = (next_first [M], init [De], next_out [M,De]): also write the next observe step's reset blend of
     h_new (fused second output)."""
@@ -811,6 +854,38 @@ def gru_bwd(dh_new, p, gamma, beta, h, mean, rstd, dp, dh, dgamma=None, dbeta=No
             raise ValueError("dgamma size mismatch")
     _call("dv3_gru_bwd", _ptr(dh_new), lddhn, _ptr(p), ldp, _ptr(gamma), _ptr(beta), _ptr(h), ldh, _ptr(mean),
           _ptr(rstd), _ptr(dp), lddp, _ptr(dh), lddh, _ptr(dgamma), _ptr(dbeta), M, De, int(accumulate_dh), _stream())
+
+
+def gru_nonorm_fwd(p, h, h_new, *, next_blend=None):
+    """gru_fwd for a cell built with norm=False: the gates on the raw p, no row statistics.  next_blend as in gru_fwd."""
+    M, N3, ldp = _rows2d(p, "p")
+    Mh, De, ldh = _rows2d(h, "h")
+    Mn, Dn, ldhn = _rows2d(h_new, "h_new")
+    if N3 != 3 * De or Mh != M or (Mn, Dn) != (M, De):
+        raise ValueError("gru shapes mismatch")
+    if next_blend is not None:
+        nf, init, nout = next_blend
+        _contig(nf, "next_first"), _contig(init, "init")
+        Mo, Do, ldo = _rows2d(nout, "next_out")
+        if nf.numel() != M or init.numel() != De or (Mo, Do) != (M, De):
+            raise ValueError("next_blend shapes mismatch")
+        _call("dv3_gru_nonorm_fwd_blend", _ptr(p), ldp, _ptr(h), ldh, _ptr(h_new), ldhn, M, De, _ptr(nf), _ptr(init),
+              _ptr(nout), ldo, _stream(), key="dv3_gru_nonorm_fwd")
+        return h_new
+    _call("dv3_gru_nonorm_fwd", _ptr(p), ldp, _ptr(h), ldh, _ptr(h_new), ldhn, M, De, _stream())
+    return h_new
+
+
+def gru_nonorm_bwd(dh_new, p, h, dp, dh, *, accumulate_dh=False):
+    M, N3, ldp = _rows2d(p, "p")
+    Mh, De, ldh = _rows2d(h, "h")
+    Mg, Dg, lddhn = _rows2d(dh_new, "dh_new")
+    Mp, Np, lddp = _rows2d(dp, "dp")
+    Md, Dd, lddh = _rows2d(dh, "dh")
+    if N3 != 3 * De or Mh != M or (Mg, Dg) != (M, De) or (Mp, Np) != (M, N3) or (Md, Dd) != (M, De):
+        raise ValueError("gru bwd shapes mismatch")
+    _call("dv3_gru_nonorm_bwd", _ptr(dh_new), lddhn, _ptr(p), ldp, _ptr(h), ldh, _ptr(dp), lddp, _ptr(dh), lddh, M, De,
+          int(accumulate_dh), _stream())
 
 
 def _groups(t, name, D):

@@ -95,6 +95,19 @@ SHAPES = {
                          dec_act="ELU",
                          p2e=dict(disag_models=3, disag_layers=2, disag_units=16, disag_target="stoch", disag_offset=1,
                                   disag_log=True, disag_action_cond=False, expl_intr_scale=1.0, expl_extr_scale=0.0)),
+    # layers without LayerNorm (configs.yaml norm / encoder.norm / decoder.norm; networks.py:53-78, 475, 551, 629, 753).
+    # Optional keys norm / enc_norm / dec_norm (default True).  tiny_nonorm_mix sets them apart (and has Gaussian
+    # latents and the one-hot actor: the dense call sites and the second actor-head route), so that a cross-wired key
+    # shows; cfg2_nonorm is the benchmark shape of the mode (bench.py --config cfg2_nonorm).
+    "tiny_nonorm": dict(stoch=4, discrete=4, deter=16, hidden=16, units=16, A=3, cnn_depth=2, B=3, T=6, H=4,
+                        actor_dist="normal", imag_gradient="dynamics", encoder="cnn", norm=False, enc_norm=False,
+                        dec_norm=False),
+    "tiny_nonorm_mix": dict(stoch=8, discrete=0, deter=16, hidden=16, units=16, A=5, cnn_depth=2, B=3, T=6, H=4,
+                            actor_dist="onehot", imag_gradient="reinforce", encoder="both", enc_mlp_units=24,
+                            enc_mlp_layers=2, norm=False, enc_norm=True, dec_norm=False),
+    "cfg2_nonorm": dict(stoch=32, discrete=32, deter=512, hidden=512, units=512, A=6, cnn_depth=32, B=16, T=64, H=15,
+                        actor_dist="normal", imag_gradient="dynamics", encoder="cnn", norm=False, enc_norm=False,
+                        dec_norm=False),
 }
 # walker_walk proprio keys, in the order the reference's obs_space dict would list them
 PROPRIO_KEYS: Tuple[Tuple[str, int], ...] = (("orientations", 14), ("height", 1), ("velocity", 9))
@@ -137,6 +150,12 @@ def make_config(name, device="cuda:0"):
         cfg["encoder"]["act"] = s["enc_act"]
     if "dec_act" in s:
         cfg["decoder"]["act"] = s["dec_act"]
+    if "norm" in s:
+        cfg["norm"] = s["norm"]
+    if "enc_norm" in s:
+        cfg["encoder"]["norm"] = s["enc_norm"]
+    if "dec_norm" in s:
+        cfg["decoder"]["norm"] = s["dec_norm"]
     cfg["encoder"]["cnn_depth"] = s["cnn_depth"]
     cfg["decoder"]["cnn_depth"] = s["cnn_depth"]
     if s["actor_dist"] == "onehot":

@@ -76,14 +76,16 @@ class Plan2Explore(nn.Module):
     # -- the fused path -----------------------------------------------------------------------------------------
     def _wants_fused(self) -> bool:
         cfg = self._config
-        return (bool(getattr(cfg, "expl_fused", True)) and cfg.disag_models >= 2 and cfg.disag_layers >= 1
-                and cfg.disag_units <= 2048)
+        return (bool(getattr(cfg, "expl_fused", True)) and bool(getattr(cfg, "norm", True)) and cfg.disag_models >= 2
+                and cfg.disag_layers >= 1 and cfg.disag_units <= 2048)
 
     def fused_reason(self):
         """None when train_fwd_bwd / train_opt can run this configuration, else why not (then `train` is the path)."""
         cfg = self._config
         if not bool(getattr(cfg, "expl_fused", True)):
             return "expl_fused is off"
+        if not bool(getattr(cfg, "norm", True)):
+            return "norm is False (the fused explorer update is built for the LayerNorm layers)"
         if cfg.disag_models < 2 or cfg.disag_layers < 1 or cfg.disag_units > 2048:
             return "ensemble shape (needs >= 2 members, >= 1 layer, <= 2048 units)"
         if self._expl_opt.bucket.members < 2:

@@ -99,6 +99,16 @@ class RewardEMA:
         return ema_vals[0].detach(), scale.detach()
 
 
+def _norm_scope(config):
+    """The scope in which networks' constructors take norm=False (networks.layernorm_free), for a config that asks for
+    it through `norm`, `encoder.norm` or `decoder.norm`; any other config builds outside it, as before."""
+    import contextlib
+
+    if config.norm and config.encoder.get("norm", True) and config.decoder.get("norm", True):
+        return contextlib.nullcontext()
+    return networks.layernorm_free()
+
+
 class WorldModel(nn.Module):
     def __init__(self, obs_space, act_space, step, config):
         super().__init__()
@@ -107,22 +117,23 @@ class WorldModel(nn.Module):
             raise NotImplementedError("the path is fp32 (configs.yaml:18, parity at 1e-4)")
         self._config = config
         shapes = {k: tuple(v.shape) for k, v in obs_space.spaces.items()}
-        self.encoder = networks.MultiEncoder(shapes, **config.encoder)
-        self.embed_size = self.encoder.outdim
-        self.dynamics = networks.RSSM(config.dyn_stoch, config.dyn_deter, config.dyn_hidden, config.dyn_rec_depth,
-                                      config.dyn_discrete, config.act, config.norm, config.dyn_mean_act,
-                                      config.dyn_std_act, config.dyn_min_std, config.unimix_ratio, config.initial,
-                                      config.num_actions, self.embed_size, config.device)
-        self.heads = nn.ModuleDict()
-        feat_size = config.dyn_stoch * (config.dyn_discrete or 1) + config.dyn_deter
-        self.heads["decoder"] = networks.MultiDecoder(feat_size, shapes, **config.decoder)
-        self.heads["reward"] = networks.MLP(
-            feat_size, (255,) if config.reward_head["dist"] == "symlog_disc" else (), config.reward_head["layers"],
-            config.units, config.act, config.norm, dist=config.reward_head["dist"],
-            outscale=config.reward_head["outscale"], device=config.device, name="Reward")
-        self.heads["cont"] = networks.MLP(
-            feat_size, (), config.cont_head["layers"], config.units, config.act, config.norm, dist="binary",
-            outscale=config.cont_head["outscale"], device=config.device, name="Cont")
+        with _norm_scope(config):
+            self.encoder = networks.MultiEncoder(shapes, **config.encoder)
+            self.embed_size = self.encoder.outdim
+            self.dynamics = networks.RSSM(config.dyn_stoch, config.dyn_deter, config.dyn_hidden, config.dyn_rec_depth,
+                                          config.dyn_discrete, config.act, config.norm, config.dyn_mean_act,
+                                          config.dyn_std_act, config.dyn_min_std, config.unimix_ratio, config.initial,
+                                          config.num_actions, self.embed_size, config.device)
+            self.heads = nn.ModuleDict()
+            feat_size = config.dyn_stoch * (config.dyn_discrete or 1) + config.dyn_deter
+            self.heads["decoder"] = networks.MultiDecoder(feat_size, shapes, **config.decoder)
+            self.heads["reward"] = networks.MLP(
+                feat_size, (255,) if config.reward_head["dist"] == "symlog_disc" else (), config.reward_head["layers"],
+                config.units, config.act, config.norm, dist=config.reward_head["dist"],
+                outscale=config.reward_head["outscale"], device=config.device, name="Reward")
+            self.heads["cont"] = networks.MLP(
+                feat_size, (), config.cont_head["layers"], config.units, config.act, config.norm, dist="binary",
+                outscale=config.cont_head["outscale"], device=config.device, name="Cont")
         if config.reward_head["dist"] != "symlog_disc":
             raise NotImplementedError("reward head: symlog_disc only")
         for name in config.grad_heads:
@@ -466,15 +477,16 @@ class ImagBehavior(nn.Module):
         self._config = config
         self._world_model = world_model
         feat_size = config.dyn_stoch * (config.dyn_discrete or 1) + config.dyn_deter
-        self.actor = networks.MLP(
-            feat_size, (config.num_actions,), config.actor["layers"], config.units, config.act, config.norm,
-            config.actor["dist"], config.actor["std"], config.actor["min_std"], config.actor["max_std"], absmax=1.0,
-            temp=config.actor["temp"], unimix_ratio=config.actor["unimix_ratio"], outscale=config.actor["outscale"],
-            name="Actor")
-        self.value = networks.MLP(
-            feat_size, (255,) if config.critic["dist"] == "symlog_disc" else (), config.critic["layers"], config.units,
-            config.act, config.norm, config.critic["dist"], outscale=config.critic["outscale"], device=config.device,
-            name="Value")
+        with _norm_scope(config):
+            self.actor = networks.MLP(
+                feat_size, (config.num_actions,), config.actor["layers"], config.units, config.act, config.norm,
+                config.actor["dist"], config.actor["std"], config.actor["min_std"], config.actor["max_std"], absmax=1.0,
+                temp=config.actor["temp"], unimix_ratio=config.actor["unimix_ratio"], outscale=config.actor["outscale"],
+                name="Actor")
+            self.value = networks.MLP(
+                feat_size, (255,) if config.critic["dist"] == "symlog_disc" else (), config.critic["layers"], config.units,
+                config.act, config.norm, config.critic["dist"], outscale=config.critic["outscale"], device=config.device,
+                name="Value")
         # (WorldModel._train finds the behaviour that follows it in an update through this list: see _auto_runner)
         _BEHAVIORS.setdefault(world_model, []).append(weakref.ref(self))
         if config.critic["dist"] != "symlog_disc" or config.actor["dist"] not in ("normal", "onehot"):
@@ -595,10 +607,10 @@ class ImagBehavior(nn.Module):
         # writes [x2pre | actor pre0 of the NEXT step] (engine.RSSMEngine.img_step_fwd, wcat)
         stack = _FUSED_IMAG and _STACK_DETER and not gauss  # (the stacked GEMM feeds the one-hot gather's base)
         cat = g("im.cat", (H, N, Hd + U0)) if stack else None
-        step = dict(x1pre=g("im.x1pre", (H, N, Hd)), m1=g("im.m1", (H, N)), r1=g("im.r1", (H, N)),
-                    x1=g("im.x1", (H, N, Hd)), gpre=g("im.gpre", (H, N, 3 * De)), mg=g("im.mg", (H, N)),
-                    rg=g("im.rg", (H, N)), x2pre=cat[..., :Hd] if stack else g("im.x2pre", (H, N, Hd)),
-                    m2=g("im.m2", (H, N)), r2=g("im.r2", (H, N)), x2=g("im.x2", (H, N, Hd)))
+        step = dict(x1pre=g("im.x1pre", (H, N, Hd)), x1=g("im.x1", (H, N, Hd)), gpre=g("im.gpre", (H, N, 3 * De)),
+                    x2pre=cat[..., :Hd] if stack else g("im.x2pre", (H, N, Hd)), x2=g("im.x2", (H, N, Hd)))
+        if dyn._norm:  # the row statistics of the three LayerNorms of img_step (norm: False has none)
+            step.update({k: g(f"im.{k}", (H, N)) for k in ("m1", "r1", "mg", "rg", "m2", "r2")})
         if stack:
             step["cat"] = cat
             wcat = g("im.wcat", (Hd + U0, De))

@@ -39,9 +39,54 @@ def _workspace(mod: nn.Module, device) -> E.Workspace:
     return ws
 
 
+# Layers without LayerNorm are opt-in.  A direct `RSSM(..., norm=False)` / `MLP` / `ConvEncoder` / `ConvDecoder` /
+# `GRUCell` keeps raising NotImplementedError, as it did before the LayerNorm-free kernels existed; inside
+# `with networks.layernorm_free():` the same call builds the reference's modules without the LayerNorm
+# (networks.py:53-78, 475, 551, 629, 753).  models.WorldModel / models.ImagBehavior open the scope themselves for a
+# config whose `norm`, `encoder.norm` or `decoder.norm` is False, so configs need nothing else; code that builds these
+# classes itself (the causal world models) opens it round its constructors.  The scope only matters at construction.
+_LN_FREE = [0]
+
+
+class layernorm_free:
+    """Context manager: constructors inside it accept norm=False.  Re-entrant; restored on exit."""
+
+    def __enter__(self):
+        _LN_FREE[0] += 1
+        return self
+
+    def __exit__(self, *exc):
+        _LN_FREE[0] -= 1
+        return False
+
+
+def _check_norm(norm, what):
+    if not norm and not _LN_FREE[0]:
+        raise NotImplementedError(f"{what}: the default is norm=True; norm=False (layers without LayerNorm) is opt-in: "
+                                  "build the module inside `with networks.layernorm_free():` (models.WorldModel and "
+                                  "models.ImagBehavior do so for a config with norm / encoder.norm / decoder.norm: False)")
+
+
+def _ln_of(mod):
+    """(weight, bias) of a LayerNorm / ImgChLayerNorm module, or (None, None) for anything else: a stack built with
+    norm=False has the activation where the LayerNorm would be (the engines read g = None as "no LayerNorm")."""
+    if isinstance(mod, ImgChLayerNorm):
+        mod = mod.norm
+    if isinstance(mod, nn.LayerNorm):
+        return mod.weight, mod.bias
+    return None, None
+
+
 def _dense_ln(seq) -> E.PDenseLN:
-    lin, norm = seq[0], seq[1]
-    return E.PDenseLN(lin.weight, norm.weight, norm.bias, getattr(seq, "_act_code", 1))
+    return E.PDenseLN(seq[0].weight, *_ln_of(seq[1]), getattr(seq, "_act_code", 1))
+
+
+def _flat(layers):
+    """[W, g, b, W, g, b, ...] as dv3hip.autograd's Functions take them (g = b = None for a layer without LayerNorm)."""
+    out = []
+    for L in layers:
+        out += [L.W, L.g, L.b]
+    return out
 
 
 def _act_module(act):
@@ -55,22 +100,27 @@ def _act_module(act):
 
 
 class GRUCell(nn.Module):
-    """networks.py:742-768: Linear(inp+size -> 3*size, no bias) + LayerNorm(3*size), update bias -1."""
+    """networks.py:742-768: Linear(inp+size -> 3*size, no bias) [+ LayerNorm(3*size) unless norm=False], update
+    bias -1."""
 
     def __init__(self, inp_size, size, norm=True, act=torch.tanh, update_bias=-1):
         super().__init__()
-        if not norm or update_bias != -1:
-            raise NotImplementedError("the fused GRU kernel implements norm=True, update_bias=-1")
-        self._inp_size, self._size = inp_size, size
+        if update_bias != -1:
+            raise NotImplementedError("the GRU kernels implement update_bias=-1")
+        _check_norm(norm, "GRUCell")
+        self._inp_size, self._size, self._norm = inp_size, size, bool(norm)
         self.layers = nn.Sequential()
         self.layers.add_module("GRU_linear", nn.Linear(inp_size + size, 3 * size, bias=False))
-        self.layers.add_module("GRU_norm", nn.LayerNorm(3 * size, eps=1e-03))
+        if norm:
+            self.layers.add_module("GRU_norm", nn.LayerNorm(3 * size, eps=1e-03))
 
     @property
     def state_size(self):
         return self._size
 
     def params(self) -> E.PDenseLN:
+        if not self._norm:
+            return E.PDenseLN(self.layers.GRU_linear.weight)
         return E.PDenseLN(self.layers.GRU_linear.weight, self.layers.GRU_norm.weight, self.layers.GRU_norm.bias)
 
     def forward(self, inputs, state):
@@ -83,8 +133,8 @@ class GRUCell(nn.Module):
         pre = torch.empty(M, 3 * self._size, device=h.device)
         ops.gemm(inputs.contiguous(), p.W, pre, A2=h)
         out = torch.empty_like(h)
-        mean, rstd = torch.empty(M, device=h.device), torch.empty(M, device=h.device)
-        ops.gru_fwd(pre, p.g, p.b, h, out, mean, rstd)
+        mean, rstd = (torch.empty(M, device=h.device), torch.empty(M, device=h.device)) if self._norm else (None, None)
+        E.gru_gates_fwd(p, pre, h, out, mean, rstd)
         return out, [out]
 
 
@@ -94,13 +144,15 @@ class DenseLNBlock(nn.Sequential):
     `1.weight`, `1.bias`), callable like the nn.Sequential it is there (scm_world_model.py:138, 160, 164): one GEMM +
     one fused LayerNorm + activation launch, through dv3hip.autograd.TrunkFn when gradients are wanted."""
 
-    def __init__(self, inp, hidden, act="SiLU"):
+    def __init__(self, inp, hidden, act="SiLU", norm=True):
+        """norm=False: [Linear(no bias), act] (networks.py:53-56: the LayerNorm is left out, the act moves up to
+        index 1, so the only state_dict key is `0.weight`)."""
         mod, code = _act_module(act)
-        super().__init__(nn.Linear(inp, hidden, bias=False), nn.LayerNorm(hidden, eps=1e-03), mod)
+        super().__init__(nn.Linear(inp, hidden, bias=False), *([nn.LayerNorm(hidden, eps=1e-03)] if norm else []), mod)
         self._act_code = code
 
     def forward(self, x):
-        W, g, b = self[0].weight, self[1].weight, self[1].bias
+        W, (g, b) = self[0].weight, _ln_of(self[1])
         if AG.wants_grad(x, W, g, b):
             return AG.TrunkFn.apply(x, self._act_code, W, g, b)
         x2 = x.reshape(-1, x.shape[-1]).to(torch.float32).contiguous()
@@ -118,18 +170,19 @@ class RSSM(nn.Module):
         discrete = int(discrete or 0)
         if not discrete:
             ops._gauss_acts(mean_act, std_act)  # (raises for an activation the head kernel does not have)
-        if not norm or rec_depth != 1 or initial != "learned":
-            raise NotImplementedError("kernels implement act=SiLU, norm=True, rec_depth=1, initial=learned")
+        if rec_depth != 1 or initial != "learned":
+            raise NotImplementedError("kernels implement rec_depth=1, initial=learned")
+        _check_norm(norm, "RSSM")
         self._act_code = _act_module(act)[1]  # (raises for an activation the kernels do not have)
         self._stoch, self._deter, self._hidden, self._discrete = stoch, deter, hidden, discrete
         self._unimix_ratio, self._num_actions, self._embed, self._device = unimix_ratio, num_actions, embed, device
-        self._min_std, self._rec_depth, self._initial = min_std, rec_depth, initial
+        self._min_std, self._rec_depth, self._initial, self._norm = min_std, rec_depth, initial, bool(norm)
         self._mean_act, self._std_act = mean_act, std_act
         stoch_w = stoch * discrete if discrete else stoch  # width of the flattened stochastic state
         stat_w = stoch * discrete if discrete else 2 * stoch  # logits, or mean_raw | std_raw (networks.py:80-91)
 
         def block(inp):
-            seq = DenseLNBlock(inp, hidden, act)
+            seq = DenseLNBlock(inp, hidden, act, norm)
             seq.apply(tools.weight_init)
             return seq
 
@@ -253,8 +306,9 @@ class RSSM(nn.Module):
     def _step_bufs(self, M, dev):
         S, D, De, Hd = self._stoch, self._discrete, self._deter, self._hidden
         mk = lambda *s: torch.empty(*s, device=dev)
-        b = dict(x1pre=mk(M, Hd), m1=mk(M), r1=mk(M), x1=mk(M, Hd), gpre=mk(M, 3 * De), mg=mk(M), rg=mk(M),
-                 deter=mk(M, De), x2pre=mk(M, Hd), m2=mk(M), r2=mk(M), x2=mk(M, Hd))
+        b = dict(x1pre=mk(M, Hd), x1=mk(M, Hd), gpre=mk(M, 3 * De), deter=mk(M, De), x2pre=mk(M, Hd), x2=mk(M, Hd))
+        if self._norm:  # (the LayerNorms' row statistics)
+            b.update(m1=mk(M), r1=mk(M), mg=mk(M), rg=mk(M), m2=mk(M), r2=mk(M))
         if not D:
             b.update(raw=mk(M, 2 * S), mean=mk(M, S), std=mk(M, S), stoch=mk(M, S), eps=mk(M, S))
         else:
@@ -454,9 +508,8 @@ class MLP(nn.Module):
                  max_std=1.0, absmax=None, temp=0.1, unimix_ratio=0.01, outscale=1.0, symlog_inputs=False,
                  device="cuda", name="NoName"):
         super().__init__()
-        if not norm:
-            raise NotImplementedError("kernels implement act=SiLU, norm=True")
-        self._act_code = _act_module(act)[1]
+        _check_norm(norm, "MLP")
+        self._act_code, self._norm = _act_module(act)[1], bool(norm)
         self._shape = (shape,) if isinstance(shape, int) else shape
         if self._shape is not None and not isinstance(self._shape, dict) and len(self._shape) == 0:
             self._shape = (1,)
@@ -466,7 +519,8 @@ class MLP(nn.Module):
         self.layers = nn.Sequential()
         for i in range(layers):
             self.layers.add_module(f"{name}_linear{i}", nn.Linear(inp_dim, units, bias=False))
-            self.layers.add_module(f"{name}_norm{i}", nn.LayerNorm(units, eps=1e-03))
+            if norm:
+                self.layers.add_module(f"{name}_norm{i}", nn.LayerNorm(units, eps=1e-03))
             self.layers.add_module(f"{name}_act{i}", _act_module(act)[0])
             inp_dim = units
         self.layers.apply(tools.weight_init)
@@ -486,8 +540,9 @@ class MLP(nn.Module):
 
     def trunk_params(self):
         nm = self._name
-        return [E.PDenseLN(getattr(self.layers, f"{nm}_linear{i}").weight, getattr(self.layers, f"{nm}_norm{i}").weight,
-                           getattr(self.layers, f"{nm}_norm{i}").bias, self._act_code) for i in range(self._n_layers)]
+        return [E.PDenseLN(getattr(self.layers, f"{nm}_linear{i}").weight,
+                           *_ln_of(getattr(self.layers, f"{nm}_norm{i}", None)), self._act_code)
+                for i in range(self._n_layers)]
 
     def params(self, key=None) -> E.PMLP:
         out = out2 = None
@@ -527,9 +582,7 @@ class MLP(nn.Module):
         x = features.to(torch.float32)
         if self._symlog_inputs:
             x = tools.symlog(x)  # inputs are data for every caller: no gradient through the symlog
-        flat = []
-        for P in self.trunk_params():
-            flat += [P.W, P.g, P.b]
+        flat = _flat(self.trunk_params())
         h = AG.TrunkFn.apply(x, self._act_code, *flat) if flat else x
         if self._shape is None:
             return h
@@ -591,8 +644,9 @@ class ImgChLayerNorm(nn.Module):
 class ConvEncoder(nn.Module):
     def __init__(self, input_shape, depth=32, act="SiLU", norm=True, kernel_size=4, minres=4):
         super().__init__()
-        if not norm or kernel_size != 4:
-            raise NotImplementedError("kernels implement act=SiLU, norm=True, kernel_size=4")
+        if kernel_size != 4:
+            raise NotImplementedError("kernels implement kernel_size=4")
+        _check_norm(norm, "ConvEncoder")
         self._act_code = _act_module(act)[1]
         h, w, input_ch = input_shape
         stages = int(np.log2(h) - np.log2(minres))
@@ -600,17 +654,19 @@ class ConvEncoder(nn.Module):
         mods = []
         for _ in range(stages):
             mods += [Conv2dSamePad(in_channels=in_dim, out_channels=out_dim, kernel_size=4, stride=2, bias=False),
-                     ImgChLayerNorm(out_dim), _act_module(act)[0]]
+                     *([ImgChLayerNorm(out_dim)] if norm else []), _act_module(act)[0]]
             in_dim, out_dim = out_dim, out_dim * 2
             h, w = h // 2, w // 2
         self.outdim = out_dim // 2 * h * w
         self._size, self._stages = input_shape[0], stages
+        self._per = 3 if norm else 2  # modules per stage: conv [, ImgChLayerNorm], act (networks.py:465-477)
         self.layers = nn.Sequential(*mods)
         self.layers.apply(tools.weight_init)
 
     def conv_params(self):
-        return [E.PConvLayer(self.layers[3 * i].weight, self.layers[3 * i + 1].norm.weight,
-                             self.layers[3 * i + 1].norm.bias, act=self._act_code) for i in range(self._stages)]
+        n = self._per
+        return [E.PConvLayer(self.layers[n * i].weight, *_ln_of(self.layers[n * i + 1]), act=self._act_code)
+                for i in range(self._stages)]
 
     @property
     def engine(self) -> E.ConvEncoderEngine:
@@ -622,10 +678,7 @@ class ConvEncoder(nn.Module):
         lead = obs.shape[:-3]
         x = (obs.to(torch.float32) - 0.5).reshape((-1,) + tuple(obs.shape[-3:])).contiguous()
         if AG.wants_grad(*self.parameters()):
-            flat = []
-            for L in self.conv_params():
-                flat += [L.W, L.g, L.b]
-            emb = AG.ConvEncoderFn.apply(x, self._size, self._act_code, *flat)
+            emb = AG.ConvEncoderFn.apply(x, self._size, self._act_code, *_flat(self.conv_params()))
             return emb.reshape(tuple(lead) + (emb.shape[-1],))
         emb = self.engine.forward(x_f32=x, keep=False)
         return emb.reshape(tuple(lead) + (emb.shape[-1],)).clone()
@@ -635,8 +688,9 @@ class ConvDecoder(nn.Module):
     def __init__(self, feat_size, shape=(3, 64, 64), depth=32, act="SiLU", norm=True, kernel_size=4, minres=4,
                  outscale=1.0, cnn_sigmoid=False):
         super().__init__()
-        if not norm or kernel_size != 4 or cnn_sigmoid:
-            raise NotImplementedError("kernels implement act=SiLU, norm=True, kernel_size=4, cnn_sigmoid=False")
+        if kernel_size != 4 or cnn_sigmoid:
+            raise NotImplementedError("kernels implement kernel_size=4, cnn_sigmoid=False")
+        _check_norm(norm, "ConvDecoder")
         self._act_code = _act_module(act)[1]  # (act: a torch.nn name, or a class as the reference's default nn.ELU)
         self._shape, self._minres = shape, minres
         layer_num = int(np.log2(shape[1]) - np.log2(minres))
@@ -651,21 +705,21 @@ class ConvDecoder(nn.Module):
             out_dim = shape[0] if last else in_dim // 2
             mods.append(nn.ConvTranspose2d(in_dim, out_dim, 4, 2, padding=(1, 1), output_padding=(0, 0), bias=last))
             if not last:
-                mods += [ImgChLayerNorm(out_dim), _act_module(act)[0]]
+                mods += [*([ImgChLayerNorm(out_dim)] if norm else []), _act_module(act)[0]]
             in_dim = out_dim
         for m in mods[:-1]:
             m.apply(tools.weight_init)
         mods[-1].apply(tools.uniform_weight_init(outscale))
         self.layers = nn.Sequential(*mods)
         self._layer_num = layer_num
+        self._per = 3 if norm else 2  # modules per hidden layer: transposed conv [, ImgChLayerNorm], act (networks.py:528-554)
 
     def conv_params(self):
-        out = []
+        out, n = [], self._per
         for i in range(self._layer_num - 1):
-            out.append(E.PConvLayer(self.layers[3 * i].weight, self.layers[3 * i + 1].norm.weight,
-                                    self.layers[3 * i + 1].norm.bias, act=self._act_code))
-        lastm = self.layers[3 * (self._layer_num - 1)]
-        out.append(E.PConvLayer(lastm.weight, None, None, lastm.bias))
+            out.append(E.PConvLayer(self.layers[n * i].weight, *_ln_of(self.layers[n * i + 1]), act=self._act_code))
+        lastm = self.layers[n * (self._layer_num - 1)]
+        out.append(E.PConvLayer(lastm.weight, None, None, lastm.bias, out=True))
         return out
 
     @property
@@ -679,10 +733,7 @@ class ConvDecoder(nn.Module):
         lead = features.shape[:-1]
         if AG.wants_grad(features, *self.parameters()):
             L = self.conv_params()
-            flat = [self._linear_layer.weight, self._linear_layer.bias]
-            for l in L[:-1]:
-                flat += [l.W, l.g, l.b]
-            flat += [L[-1].W, L[-1].bias]
+            flat = [self._linear_layer.weight, self._linear_layer.bias] + _flat(L[:-1]) + [L[-1].W, L[-1].bias]
             rec = AG.ConvDecoderFn.apply(features.reshape(-1, features.shape[-1]), self._minres, self._act_code, *flat)
             return rec.reshape(tuple(lead) + tuple(rec.shape[1:]))
         x = features.reshape(-1, features.shape[-1]).to(torch.float32).contiguous()

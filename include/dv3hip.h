@@ -147,6 +147,27 @@ int dv3_gru_bwd(const float* dh_new, long lddhn, const float* p, long ldp, const
                 const float* h, long ldh, const float* mean, const float* rstd, float* dp, long lddp, float* dh,
                 long lddh, float* dgamma, float* dbeta, int M, int De, int accumulate_dh, void* stream);
 
+/* ---- layers without a LayerNorm (norm / encoder.norm / decoder.norm: False) ------------------------
+ * The reference then leaves out the nn.LayerNorm / ImgChLayerNorm module and nothing else: every trunk Linear, conv
+ * and transposed conv keeps bias=False, so a layer is act(W x) (networks.py:53-78, 472, 529-548, 627-633).
+ * dv3_act_fwd: y = act(x);  dv3_act_bwd: dx (+)= dy * act'(x).  Rows of any length N with row strides
+ * ldx / ldy / lddy / lddx >= N, act and chw_group (y in fwd, dy in bwd; then R % chw_group == 0) as in dv3_ln_act_*;
+ * no row statistics and no parameter gradients.  dx may be dy.  16-byte accesses where N % 4 == 0, the strides are
+ * multiples of 4 and the pointers 16-byte aligned; scalar otherwise. */
+int dv3_act_fwd(const float* x, long ldx, float* y, long ldy, long R, int N, int act, int chw_group, void* stream);
+int dv3_act_bwd(const float* dy, long lddy, const float* x, long ldx, float* dx, long lddx, long R, int N, int act,
+                int chw_group, int accumulate_dx, void* stream);
+/* GRUCell.forward with norm=False (networks.py:751-754, 760-768): the raw p [M,3*De] is split into r | c | u, then
+ * r=sigmoid(r), c=tanh(r*c), u=sigmoid(u-1), h' = u*c + (1-u)*h.  Any De, forward and backward (no row reduction).
+ * dv3_gru_nonorm_fwd_blend: plus the next observe step's reset blend as in dv3_gru_fwd_blend, for the same De.
+ * bwd: dp = (dp_r | dp_c | dp_u) is overwritten, dh overwritten or accumulated; dh may be dh_new. */
+int dv3_gru_nonorm_fwd(const float* p, long ldp, const float* h, long ldh, float* h_new, long ldhn, int M, int De,
+                       void* stream);
+int dv3_gru_nonorm_fwd_blend(const float* p, long ldp, const float* h, long ldh, float* h_new, long ldhn, int M, int De,
+                             const float* next_first, const float* init, float* next_out, long ld_next, void* stream);
+int dv3_gru_nonorm_bwd(const float* dh_new, long lddhn, const float* p, long ldp, const float* h, long ldh, float* dp,
+                       long lddp, float* dh, long lddh, int M, int De, int accumulate_dh, void* stream);
+
 /* ---- one-hot categorical with unimix -- tools.OneHotDist (tools.py:436-460) -----------------------
  * R groups of D <= 64 classes.  sample: onehot(argmax p_hat/q), q = noise[R,D] ~ Exp(1) when given,
  * else Philox draws from rng_state = {seed, offset} (device memory).  mode=1: onehot(argmax p_hat).
