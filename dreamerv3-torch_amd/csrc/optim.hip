@@ -161,7 +161,10 @@ __global__ __launch_bounds__(1024) void quantile2_ema_kernel(const float* __rest
   __shared__ float frac[2];
   const int tid = threadIdx.x, wave = tid >> 6;
   if (tid == 0) {
-    // ranks in float32 as torch.quantile computes them (q is a float32 tensor, models.py:16: ranks = q * (n - 1))
+    // ranks in float32 as torch.quantile computes them (q is a float32 tensor, models.py:16: ranks = q * (n - 1)).
+    // No contraction here: fused into p - floorf(p), the unrounded product gave another interpolation weight than
+    // torch's rounded rank (up to 2^-12 at n = 8192: 4 ulp of the 95 % quantile).
+#pragma clang fp contract(off)
     const float p0 = (float)q0 * (float)(n - 1), p1 = (float)q1 * (float)(n - 1);
     rank[0] = (long)floorf(p0); rank[1] = (long)ceilf(p0);
     rank[2] = (long)floorf(p1); rank[3] = (long)ceilf(p1);

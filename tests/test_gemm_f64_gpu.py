@@ -73,8 +73,9 @@ Three things the guards make unreachable, found while copying them (the rows use
 
 Out of scope (development switches; DV3_ENV_INT / _dev.value are constants unless the library is built with
 build.py --dev): DV3_DIRECT_* (RN 2 / 8, other batch depths, PIPE), DV3_L16_* (serial loop, serial epilogue, PF 2),
-DV3_GROUP_TILE, DV3_XCD_M, DV3_SMALL_TILE / DV3_MID_TILE, DV3_BT_MIN_FLOPS.  Also: the fused epilogues (gemm_sample,
-scan_*_gemm), ens_gemm, K = 0, lane tile choices.
+DV3_GROUP_TILE, DV3_XCD_M, DV3_SMALL_TILE / DV3_MID_TILE, DV3_BT_MIN_FLOPS.  Also: K = 0, lane tile choices.
+Covered elsewhere: the scan epilogues (scan_*_gemm) in tests/test_ln_gru_f64_gpu.py, gemm_sample (EPI 1, ALN 1, its
+[A | A2] seam) in tests/test_fused_f64_gpu.py, ens_gemm in tests/test_ens_f64_gpu.py.
 
 Bars: 1e-4 * max(1, max |ref|) (TOL of tests/test_kernels_gpu.py, check() of tests/test_row_kernels_f64_gpu.py) for
 every float comparison.  No bar here is widened: on every case below the fp32 CPU oracle's own error against float64
@@ -316,7 +317,7 @@ def c_dispatch(ta, tb, M, N, K, K1, hasA2, bias, acc, tile, l16ok):
 
 
 # every kernel instantiation the shipped library reaches from dv3_gemm_f32, dv3_gemm_split_f32 and
-# dv3_gemm_tn_grouped_f32 (the EPI / ALN forms belong to dv3_gemm_sample_f32: out of scope)
+# dv3_gemm_tn_grouped_f32 (the EPI / ALN forms belong to dv3_gemm_sample_f32: tests/test_fused_f64_gpu.py)
 REACHABLE = ({f"gemm_kernel<{t},{o}>" for t in TS for o in ORIENT} |
              {f"skinny<{tb},{mt},{b}>" for tb in "TN" for mt, bs in ((1, (3, 6, 12)), (2, (3, 6))) for b in bs} |
              {f"nn64<{mt},{b}>" for mt in (1, 2) for b in (2, 4)} | {"direct<T>", "direct<N>", "direct_tn", "grouped"} |
