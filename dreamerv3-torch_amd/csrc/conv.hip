@@ -918,6 +918,117 @@ __global__ __launch_bounds__(256) void conv_s2_c3_mfma_kernel(const float* __res
       }
 }
 
+// The same product for frames whose output rows divide a 128-pixel tile (OW = 16, 32 or 64, OH a multiple of 128 / OW:
+// every shipped frame size).  The tile is then R = 128 / OW whole output rows of ONE image and its receptive field is
+// the 2 R + 2 contiguous image rows around them: they are staged in LDS with aligned 16-byte loads of the rows as they
+// lie in memory, so every input byte enters the CU once instead of four times through 12-byte-strided loads.  The 12
+// floats (kx, c) of a pixel's kernel row start 24 ox bytes into the padded row, 16-byte aligned only for even ox: the
+// band is kept TWICE, the second copy two floats further right, and the odd pixels read that one -- each fragment is
+// one ds_read_b128 straight from the band, there is no A tile.  The MFMA operands are swapped (rows = channels,
+// columns = pixels), so a lane ends up with FOUR CONSECUTIVE CHANNELS of one pixel: the output leaves in 16-byte
+// stores, 64 contiguous bytes per pixel per instruction, with no transpose.  Same products, same k order (ky, kx, c
+// in 16-k chunks) as conv_s2_c3_mfma_kernel: the results are bit-equal.  25 KB of LDS (38 at CW = 96) instead of 33
+// (46): 6 workgroups per CU instead of 4 at CW = 32.
+constexpr int kC3BandMax = 6 * (3 * 128 + 8);  // floats of one copy of the band: OW 16 / 32 / 64 -> 1872 / 2000 / 2352
+
+template <int CW>
+__global__ __launch_bounds__(256) void conv_s2_c3_band_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                              float* __restrict__ y, int H, int W, int lgOW,
+                                                              int accumulate) {
+  constexpr int LD = 52, TN = CW / 16;
+  __shared__ __attribute__((aligned(16))) float Xs[2 * kC3BandMax];
+  __shared__ __attribute__((aligned(16))) float Bs[CW * LD];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int i = lane & 15, q = lane >> 4;
+  const int OW = 1 << lgOW, R = 128 >> lgOW, NR = 2 * R + 2, RS = 3 * W + 8;
+  const int tpi = (H / 2) / R;  // tiles per image
+  const int n = blockIdx.x / tpi, oy0 = (blockIdx.x - n * tpi) * R;
+  const float* xin = x + (long)n * H * W * 3;
+  // band row rr = image row 2 oy0 - 1 + rr; image float j of the row sits at Xs[rr * RS + 3 + j] and, in the second
+  // copy, at Xs[kC3BandMax + rr * RS + 5 + j]; the pixels left and right of the row (ix = -1, W) are zeros
+  constexpr int NJ = 3;           // float4 per thread: (2 R + 2) * 3 W / 4 = 432 / 480 / 576 <= 3 * 256
+  const int V = 3 << (lgOW - 1);  // float4 per row, 3 W / 4
+  f32x4 xv[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const int f = tid + 256 * j;
+    const int rr = (f >> (lgOW - 1)) / 3, m = f - rr * V;
+    const int iy = 2 * oy0 - 1 + rr;
+    xv[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    if (rr < NR && iy >= 0 && iy < H) xv[j] = *reinterpret_cast<const f32x4*>(xin + ((long)iy * W * 3 + 4 * m));
+  }
+  for (int e = tid; e < CW * 48; e += 256) {  // w[co][c][ky][kx] -> Bs[co][ky*12 + kx*3 + c]
+    const int co = e / 48, r = e - co * 48;
+    const int c = r >> 4, ky = (r >> 2) & 3, kx = r & 3;
+    Bs[co * LD + ky * 12 + kx * 3 + c] = w[e];
+  }
+  if (tid < NR) {
+    float* r0 = &Xs[tid * RS];
+    float* r1 = r0 + kC3BandMax;
+#pragma unroll
+    for (int e = 0; e < 3; ++e) {
+      r0[e] = 0.f;
+      r0[3 * W + 3 + e] = 0.f;
+      r1[2 + e] = 0.f;
+      r1[3 * W + 5 + e] = 0.f;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const int f = tid + 256 * j;
+    const int rr = (f >> (lgOW - 1)) / 3, m = f - rr * V;
+    if (rr < NR) {
+      float* d0 = &Xs[rr * RS + 3 + 4 * m];
+      float* d1 = d0 + kC3BandMax + 2;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        d0[e] = xv[j][e];
+        d1[e] = xv[j][e];
+      }
+    }
+  }
+  __syncthreads();
+  // this lane's pixels: tile pixel wave * 32 + 16 a + i = (output row r, column ox) -- 16 divides OW, so a row block
+  // of 16 pixels lies in one output row
+  int xo[2];
+#pragma unroll
+  for (int a = 0; a < 2; ++a) {
+    const int pl = wave * 32 + 16 * a + i;
+    const int r = pl >> lgOW, ox = pl & (OW - 1);
+    xo[a] = 2 * r * RS + 6 * ox + ((ox & 1) ? kC3BandMax + 2 : 0);
+  }
+  f32x4 acc[2][TN];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < TN; ++b) acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const int k0 = 16 * c + 4 * q, ky = k0 / 12, rem = k0 - 12 * ky;
+    f32x4 xf[2], wf[TN];
+#pragma unroll
+    for (int a = 0; a < 2; ++a) xf[a] = *reinterpret_cast<const f32x4*>(&Xs[xo[a] + ky * RS + rem]);
+#pragma unroll
+    for (int b = 0; b < TN; ++b) wf[b] = *reinterpret_cast<const f32x4*>(&Bs[(16 * b + i) * LD + 16 * c + 4 * q]);
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+      for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < TN; ++b)
+          acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[b][g], xf[a][g], acc[a][b], 0, 0, 0);
+  }
+  // acc[a][b][r]: channel 16 b + 4 q + r of pixel 16 a + i
+  float* yt = y + ((long)blockIdx.x * 128 + wave * 32 + i) * CW + 4 * q;
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < TN; ++b) {
+      f32x4* o = reinterpret_cast<f32x4*>(yt + (long)16 * a * CW + 16 * b);
+      *o = accumulate ? (*o + acc[a][b]) : acc[a][b];
+    }
+}
+
 // y[n,2y2+py,2x2+px,co<3] = sum_{a,b,ci<CW} x[n,y2+py-a,x2+px-b,ci] * w[ci][co][1-py+2a][1-px+2b] + bias + add
 // (ConvTranspose2d CW -> 3).  One thread per input-grid pixel computes its 2x2 output block.
 template <int CW>
@@ -986,10 +1097,15 @@ __global__ __launch_bounds__(256) void convT_s2_c3_kernel(const float* __restric
 // 4 x 4 x 3 output patch at (2 iy - 1, 2 ix - 1) -- Wm[ci][(co, ky, kx)] is the ConvTranspose2d weight as stored.  That is
 // a dense GEMM M = pixels, K = CW, N = 48 (three 16-column MFMA blocks, no padding of the 3 output channels to 16) whose
 // A rows are the NHWC pixels themselves (one 16-byte global load per lane per 16-k chunk, all of a wave's row blocks
-// in flight together, no staging), followed by the overlap-add of the patches: a workgroup owns a 16 x 16 input tile
-// (+ one pixel of halo: 324 GEMM rows in 21 row blocks over its 4 waves), writes the products P[pixel][48] to LDS
-// and every thread then GATHERS the four terms of each of its 12 outputs of the 32 x 32 x 3 tile, stored as 384-byte
-// rows.  (Adding the patches into an LDS tile with ds_add_f32 instead measured 266 us: LDS float atomics retire about
+// in flight together, no staging), followed by the overlap-add of the patches: a workgroup owns an 8-row x 16-column
+// input tile (+ one pixel of halo: 180 GEMM rows in 12 row blocks, three per wave), writes the products P[pixel][48]
+// to LDS and every thread then GATHERS the four terms of each of its 6 outputs of the 16 x 32 x 3 tile, stored as
+// 384-byte rows.  The MFMA operands are swapped (rows = the 48 columns of Wm, columns = pixels): a lane holds four
+// consecutive columns (kx = 0..3) of one pixel and P is written with ds_write_b128.  P is 39 KB: FOUR workgroups per
+// CU -- the 16 x 16 tile this kernel had first (324 rows in 21 blocks, 5.25 per wave, 70 KB of P) left two, and its
+// load -> MFMA -> gather phases, strictly one after the other inside a workgroup, had too few neighbours to overlap
+// with.  Same products in the same order per output: bit-equal to that form.
+// (Adding the patches into an LDS tile with ds_add_f32 instead measured 266 us: LDS float atomics retire about
 // two lanes per clock; the thread-per-pixel VALU form above: 178 us for 1024 frames; HBM floor of the layer: ~25 us.)
 template <int CW>
 __global__ __launch_bounds__(256) void convT_s2_c3_mfma_kernel(const float* __restrict__ x, const float* __restrict__ w,
@@ -997,16 +1113,17 @@ __global__ __launch_bounds__(256) void convT_s2_c3_mfma_kernel(const float* __re
                                                                float* __restrict__ y, int Nimg, int IH, int IW,
                                                                int accumulate) {
   constexpr int NCH = CW / 16;
-  constexpr int RB = (18 * 18 + 15) / 16;  // 21 row blocks of 16 tile pixels (halo included)
-  constexpr int LDP = 52;                  // row stride of P: the four 4-row groups of a store land 16 banks apart
-  __shared__ float P[RB * 16 * LDP];
+  constexpr int TR = 8, NPIX = (TR + 2) * 18;  // input rows of the tile; tile pixels, halo included
+  constexpr int RB = (NPIX + 15) / 16;         // 12 row blocks of 16 tile pixels
+  constexpr int LDP = 52;                      // row stride of P: 13 16-byte slots, the 16 pixels of a store land apart
+  __shared__ __attribute__((aligned(16))) float P[RB * 16 * LDP];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int i = lane & 15, q = lane >> 4;
-  const int tx_n = IW / 16, ty_n = IH / 16;
+  const int tx_n = IW / 16, ty_n = IH / TR;
   const int img = blockIdx.x / (tx_n * ty_n), trem = blockIdx.x % (tx_n * ty_n);
   const int ty = trem / tx_n, tx = trem % tx_n;
   const float* xin = x + (long)img * IH * IW * CW;
-  // B fragments: Wm[k = 16 c + 4 q + g][n = 16 b + i]
+  // weight fragments: Wm[k = 16 c + 4 q + g][n = 16 b + i]
   f32x4 bf[NCH][3];
 #pragma unroll
   for (int c = 0; c < NCH; ++c)
@@ -1014,7 +1131,7 @@ __global__ __launch_bounds__(256) void convT_s2_c3_mfma_kernel(const float* __re
     for (int b = 0; b < 3; ++b)
 #pragma unroll
       for (int g = 0; g < 4; ++g) bf[c][b][g] = w[(long)(16 * c + 4 * q + g) * 48 + 16 * b + i];
-  constexpr int RPW = (RB + 3) / 4;        // row blocks per wave (6), loaded JB at a time: ONE memory round trip per batch
+  constexpr int RPW = (RB + 3) / 4;        // row blocks per wave (3), loaded JB at a time: ONE memory round trip per batch
   constexpr int JB = NCH <= 2 ? RPW : 2;
   for (int j0 = 0; j0 < RPW; j0 += JB) {
     f32x4 af[JB][NCH];
@@ -1023,8 +1140,8 @@ __global__ __launch_bounds__(256) void convT_s2_c3_mfma_kernel(const float* __re
     for (int j = 0; j < JB; ++j) {
       const int pl = (wave + 4 * (j0 + j)) * 16 + i;  // the pixel this lane loads
       const int ly = pl / 18, lx = pl % 18;
-      const int gy = ty * 16 + ly - 1, gx = tx * 16 + lx - 1;
-      const bool ok = pl < 18 * 18 && gy >= 0 && gy < IH && gx >= 0 && gx < IW;
+      const int gy = ty * TR + ly - 1, gx = tx * 16 + lx - 1;
+      const bool ok = pl < NPIX && gy >= 0 && gy < IH && gx >= 0 && gx < IW;
       const float* src = xin + ((long)(ok ? gy : 0) * IW + (ok ? gx : 0)) * CW + 4 * q;
 #pragma unroll
       for (int c = 0; c < NCH; ++c) af[j][c] = *reinterpret_cast<const f32x4u*>(src + 16 * c);
@@ -1043,12 +1160,10 @@ __global__ __launch_bounds__(256) void convT_s2_c3_mfma_kernel(const float* __re
         for (int g = 0; g < 4; ++g)
 #pragma unroll
           for (int b = 0; b < 3; ++b)
-            acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[j][c][g] * msk[j], bf[c][b][g], acc[b], 0, 0, 0);
-      // acc[b][r]: tile pixel rbk * 16 + 4 q + r, column 16 b + i
+            acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(bf[c][b][g], af[j][c][g] * msk[j], acc[b], 0, 0, 0);
+      // acc[b][r]: column 16 b + 4 q + r of tile pixel rbk * 16 + i
 #pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int b = 0; b < 3; ++b) P[(rbk * 16 + 4 * q + r) * LDP + 16 * b + i] = acc[b][r];
+      for (int b = 0; b < 3; ++b) *reinterpret_cast<f32x4*>(&P[(rbk * 16 + i) * LDP + 16 * b + 4 * q]) = acc[b];
     }
   }
   __syncthreads();
@@ -1056,7 +1171,7 @@ __global__ __launch_bounds__(256) void convT_s2_c3_mfma_kernel(const float* __re
   const int OH = 2 * IH, OW = 2 * IW;
   const float bb[3] = {(bias ? bias[0] : 0.f) + out_add, (bias ? bias[1] : 0.f) + out_add, (bias ? bias[2] : 0.f) + out_add};
 #pragma unroll 4
-  for (int f = tid; f < 32 * 32 * 3; f += 256) {
+  for (int f = tid; f < 2 * TR * 32 * 3; f += 256) {
     const int oy = f / 96, col = f % 96;
     const int ox = col / 3, c = col % 3;
     const int ky0 = (oy + 1) & 1, kx0 = (ox + 1) & 1;
@@ -1069,7 +1184,7 @@ __global__ __launch_bounds__(256) void convT_s2_c3_mfma_kernel(const float* __re
         const int ly = (oy + 3 - ky) >> 1, lx = (ox + 3 - kx) >> 1;
         v += P[(ly * 18 + lx) * LDP + c * 16 + ky * 4 + kx];
       }
-    float* o = y + (((long)img * OH + 32 * ty + oy) * OW + 32 * tx) * 3 + col;
+    float* o = y + (((long)img * OH + 2 * TR * ty + oy) * OW + 32 * tx) * 3 + col;
     *o = accumulate ? (*o + v) : v;
   }
 }
@@ -1899,6 +2014,17 @@ extern "C" int dv3_conv_s2_c3_fwd(const float* x, const float* w, float* y, int 
   if (blocks > 16384) blocks = 16384;
   hipStream_t s = (hipStream_t)stream;
   static const int env_mfma = DV3_ENV_INT("DV3_C3_MFMA", 1);
+  static const int env_band = DV3_ENV_INT("DV3_C3_BAND", 1);
+  const int OW = W / 2;
+  // whole output rows in a 128-pixel tile of one image, image rows and output pixels 16-byte aligned: the band kernel
+  if (env_mfma && env_band && (CW == 32 || CW == 96) && total < 0x7fffffffL * 64 && (OW == 16 || OW == 32 || OW == 64) &&
+      (H / 2) % (128 / OW) == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0) {
+    const dim3 grid((unsigned)(total / 128));
+    const int lgOW = OW == 16 ? 4 : OW == 32 ? 5 : 6;
+    if (CW == 32) hipLaunchKernelGGL((conv_s2_c3_band_kernel<32>), grid, dim3(256), 0, s, x, w, y, H, W, lgOW, accumulate);
+    else hipLaunchKernelGGL((conv_s2_c3_band_kernel<96>), grid, dim3(256), 0, s, x, w, y, H, W, lgOW, accumulate);
+    return (int)hipGetLastError();
+  }
   if (env_mfma && (CW == 32 || CW == 96) && total < 0x7fffffffL * 64) {
     const dim3 grid((unsigned)((total + 127) / 128));
     if (CW == 32) hipLaunchKernelGGL((conv_s2_c3_mfma_kernel<32>), grid, dim3(256), 0, s, x, w, y, Nimg, H, W, accumulate);
@@ -1920,7 +2046,7 @@ extern "C" int dv3_convT_s2_c3_fwd(const float* x, const float* w, const float* 
   hipStream_t s = (hipStream_t)stream;
   static const int env_c3t = DV3_ENV_INT("DV3_C3T_MFMA", 1);
   if (env_c3t && (IH % 16) == 0 && (IW % 16) == 0 && (CW == 32 || CW == 96)) {
-    const dim3 grid((unsigned)((long)Nimg * (IH / 16) * (IW / 16)));
+    const dim3 grid((unsigned)((long)Nimg * (IH / 8) * (IW / 16)));  // 8-row x 16-column input tiles
     if (CW == 32) hipLaunchKernelGGL((convT_s2_c3_mfma_kernel<32>), grid, dim3(256), 0, s, x, w, bias, out_add, y, Nimg, IH, IW, accumulate);
     else hipLaunchKernelGGL((convT_s2_c3_mfma_kernel<96>), grid, dim3(256), 0, s, x, w, bias, out_add, y, Nimg, IH, IW, accumulate);
     return (int)hipGetLastError();
